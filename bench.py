@@ -7,7 +7,10 @@ tol_mu 1e-16).  Multi-GPU: one process per GPU (torch.distributed.run), each ran
 shard of independent problems — no data-path collective (scaling "weak"); the RCCL gather of the
 solutions to rank 0 is timed separately and reported as gather_ms.
 
-Prints ONE JSON line on rank 0 (the driver's contract), with two extra objects:
+Prints ONE JSON line on rank 0 (the driver's contract).  A plain run sets up, warms up, times
+--steps steps and prints the headline figures (value, ms_per_step, ...); --dump-outputs DIR also
+writes the arrays the last timed step returned to DIR/<name>.npy.  Everything else the benchmark
+measures runs only with --full, which adds to the line gather_ms (multi-GPU) and two objects:
   roofline      HBM roofline of the dominant kernel (dcm_mpc_cold_kernel: the fp32 active-set
                 search and the fp64 certified passes), from the algorithmic bytes per QP
                  and the kernel's average duration measured with HIP events
@@ -94,6 +97,46 @@ def valu_issue(kernel_ms):
 
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X vector fp64 (MI355X_MICROARCH.md)
+
+
+def qp_roofline(kernel_ms, B, N, M, out):
+    """--full: the `roofline` object of the default workload's line.  kernel_ms: the timed steps'
+    HIP-event time per step (one launch per step on the launch stream); out: the last step's
+    solution (its iteration counts and polish flags)."""
+    import torch
+    bpq = algorithmic_bytes_per_qp(N, M)
+    achieved = bpq * B / (kernel_ms * 1e-3) / 1e9
+    traffic, traffic_src = profiled_traffic()
+    # executed fp64 flops of the dominant kernel's launch from the committed SQ pass (FMA
+    # counts two, 64 lanes per wave instruction, masked lanes included): the active-set
+    # passes' scans with their Kogge-Stone redundancy, i.e. what the SIMDs actually did
+    pmc, _ = profiled_summary()
+    f64 = ((pmc or {}).get("valu_issue") or {}).get("fp64_insts_per_launch")
+    fp64_exec_tf = (64.0 * (2.0 * f64["fma"] + f64["mul"] + f64["add"]) / (kernel_ms * 1e-3)
+                    / 1e12) if f64 else None
+    vi = valu_issue(kernel_ms)
+    # "bound": the roof that binds the kernel as measured (VALU issue and latency,
+    # DESIGN.md 3.1), not HBM; achieved / peak / frac stay the HBM stream the contract
+    # prices (algorithmic bytes over the kernel time against 8 TB/s)
+    return {"bound": "valu_issue", "achieved": achieved, "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_source": traffic_src,
+            "kernel": "dcm_mpc_cold_kernel<2> (fp32 active-set search + fp64 "
+                      "certified passes; + the IPM kernel's stage 2 on the QPs it hands "
+                      "over, inside the same event pair)",
+            "kernel_ms": kernel_ms,
+            "bytes_per_qp": bpq,
+            # what binds this kernel is neither HBM nor MFMA: VALU issue and the
+            # latency of the scans' lane-shuffle chains (DESIGN.md 3.1)
+            "binding_roof": {"kind": "valu_issue",
+                             "frac": vi["frac"] if vi else None},
+            "valu_issue": vi,
+            "fp64_valu": {"executed_tflops": fp64_exec_tf,
+                          "peak_tflops": FP64_PEAK_TFLOPS,
+                          "executed_frac": (fp64_exec_tf / FP64_PEAK_TFLOPS
+                                            if fp64_exec_tf else None)},
+            "mean_ipm_iters": float(out["iters"].to(torch.int64).float().mean()),
+            "polished_frac": float(out["polished"].to(torch.float64).mean())}
 
 
 def fbd_sq_summary():
@@ -189,6 +232,33 @@ def host_cpu_info():
     return info
 
 
+DUMP_BYTES = 60 * 10**6   # --dump-outputs: array bytes over all ranks (files + headers < 64 MB)
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last timed step,
+    one DIR/<name>.npy each (rank r > 0 of a multi-GPU run: DIR/<name>_rank<r>.npy), float32 kept
+    and everything else as float64.  Over DUMP_BYTES (shared evenly by the ranks) every array keeps
+    the same fraction of its leading-axis rows, drawn without replacement by a generator of fixed
+    seed and sorted, so two runs with the same arguments write the same rows (arrays of equal
+    leading size the same ones)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        if isinstance(v, dict):   # a solve's input window kept beside its outputs: not an output
+            continue
+        a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+        host[k] = np.ascontiguousarray(a if a.dtype == np.float32 else a.astype(np.float64))
+    total = sum(a.nbytes for a in host.values())
+    budget = DUMP_BYTES // max(1, world)
+    for k, a in host.items():
+        if total > budget and a.ndim:
+            keep = max(1, int(a.shape[0] * budget / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, k + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def emit(line):
     """Print one JSON result line with the build provenance of the library it measured: the source
     hash compiled into lib/libblf.so (blf_version) against the hash of this tree's sources."""
@@ -207,8 +277,16 @@ def main():
                     help="QPs over all GPUs, split into contiguous per-rank shards (strong scaling; "
                          "configs[3] is --global-batch 262144 on 8 GPUs)")
     ap.add_argument("--horizon", type=int, default=100)
-    ap.add_argument("--cpu-seconds", type=float, default=5.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: the CPU baseline of the "
+                         "workload (unless --no-cpu), and on the default workload the roofline "
+                         "object and, multi-GPU, the timed RCCL gather")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed seeded sample "
+                         "of the rows of larger outputs)")
+    ap.add_argument("--cpu-seconds", type=float, default=5.0, help="--full: the CPU baseline's sample")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--dump-state", default=None,
                     help="c5: write each rank's final robot state to DIR/c5_state_rank<r>.npz")
     ap.add_argument("--c5-groups", type=int, default=2,
@@ -230,6 +308,8 @@ def main():
                          "mc: plans with three-contact phases (the reference ContactPhaseList "
                          "test's lists, 16 facet slots, N=50): cold solves and warm windows")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = True
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus != world:
         # checked before any HIP call: a scaling run launched without torch.distributed.run would
@@ -299,19 +379,18 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    kernel_ms = ev0.elapsed_time(ev1) / args.steps      # one launch per step on this stream
     if world > 1:
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu",
                          dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    iters = out["iters"].to(torch.int64)
-    polished = out["polished"].to(torch.float64)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     # RCCL gather of every rank's solutions to rank 0 (timed separately, not in `value`)
     gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         from blf import distributed as D
         dist.barrier()
         torch.cuda.synchronize()
@@ -323,17 +402,6 @@ def main():
 
     if rank == 0:
         total = world * B * args.steps
-        bpq = algorithmic_bytes_per_qp(N, M)
-        achieved = bpq * B / (kernel_ms * 1e-3) / 1e9
-        traffic, traffic_src = profiled_traffic()
-        # executed fp64 flops of the dominant kernel's launch from the committed SQ pass (FMA
-        # counts two, 64 lanes per wave instruction, masked lanes included): the active-set
-        # passes' scans with their Kogge-Stone redundancy, i.e. what the SIMDs actually did
-        pmc, _ = profiled_summary()
-        f64 = ((pmc or {}).get("valu_issue") or {}).get("fp64_insts_per_launch")
-        fp64_exec_tf = (64.0 * (2.0 * f64["fma"] + f64["mul"] + f64["add"]) / (kernel_ms * 1e-3)
-                        / 1e12) if f64 else None
-        vi = valu_issue(kernel_ms)
         line = {
             "metric": "DCM-MPC QP solves/sec (batch, horizon=100) at 1/2/4/8 MI355X",
             "value": total / elapsed,
@@ -357,30 +425,10 @@ def main():
                        "batch_per_gpu": B, "global_batch": B * world, "horizon": N,
                        "max_facets": M,
                        "parallelism": f"shard{world} (independent problems)"},
-            # "bound": the roof that binds the kernel as measured (VALU issue and latency,
-            # DESIGN.md 3.1), not HBM; achieved / peak / frac stay the HBM stream the contract
-            # prices (algorithmic bytes over the kernel time against 8 TB/s)
-            "roofline": {"bound": "valu_issue", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "kernel": "dcm_mpc_cold_kernel<2> (fp32 active-set search + fp64 "
-                                   "certified passes; + the IPM kernel's stage 2 on the QPs it hands "
-                                   "over, inside the same event pair)",
-                         "kernel_ms": kernel_ms,
-                         "bytes_per_qp": bpq,
-                         # what binds this kernel is neither HBM nor MFMA: VALU issue and the
-                         # latency of the scans' lane-shuffle chains
-                         "binding_roof": {"kind": "valu_issue",
-                                          "frac": vi["frac"] if vi else None},
-                         "valu_issue": vi,
-                         "fp64_valu": {"executed_tflops": fp64_exec_tf,
-                                       "peak_tflops": FP64_PEAK_TFLOPS,
-                                       "executed_frac": (fp64_exec_tf / FP64_PEAK_TFLOPS
-                                                         if fp64_exec_tf else None)},
-                         "mean_ipm_iters": float(iters.float().mean()),
-                         "polished_frac": float(polished.mean())},
-            "gather_ms": gather_ms,
         }
+        if args.full:
+            line["roofline"] = qp_roofline(ev0.elapsed_time(ev1) / args.steps, B, N, M, out)
+            line["gather_ms"] = gather_ms
         if not args.no_cpu:
             threads = cpu_threads()
             host = dict(prob, A=A.cpu().numpy(), b=b.cpu().numpy(), nfacets=nf.cpu().numpy())
@@ -456,6 +504,8 @@ def other_workload(args):
 
         sec = _timed(step, args.steps, args.warmup)
         assert int((out["qp"]["status"] != 0).sum()) == 0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(out["qp"], swing_pva=out["sp"][0], swing_idx=out["sp"][1]))
         line = {"metric": "DCM-MPC pipeline solves/sec (hull H-rep + QP + swing splines)",
                 "value": B / sec, "unit": "QP/s", "n_gpus": 1, "ms_per_step": sec * 1e3,
                 "steps": args.steps, "warmup": args.warmup, "dtype": "f64",
@@ -580,6 +630,9 @@ def closed_loop(args):
         os.makedirs(args.dump_state, exist_ok=True)
         np.savez(os.path.join(args.dump_state, f"c5_state_rank{rank}.npz"),
                  **{k: np.concatenate([s_[k] for s_ in states]) for k in states[0]})
+    if args.dump_outputs:   # the robot state after the last timed period, the groups in order
+        dump_outputs(args.dump_outputs,
+                     {k: np.concatenate([s_[k] for s_ in states]) for k in states[0]}, rank, world)
     stat = torch.bincount(torch.cat(statuses).to(torch.int64).cpu(), minlength=4)[:4].to(torch.float64)
     z = np.concatenate([s_["base_pos"][:, 2] for s_ in states])
     zr = torch.tensor([-z.min(), z.max(), 0.0 if finite else 1.0], dtype=torch.float64)
@@ -797,6 +850,8 @@ def single_solve_latency(args, h, dev):
         torch.cuda.synchronize()
     dev_us = float(np.median([ev[2 * i].elapsed_time(ev[2 * i + 1]) for i in range(50)])) * 1e3
     assert int(out["status"][0]) == 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle as O
     host = dict(prob)
@@ -883,6 +938,8 @@ def three_contact(args, h, dev):
     cold_unsolved = int((cold["status"] != 0).sum())
     cold_passes = float(cold["passes"].float().mean())
     cold_ipm = int((cold["iters"] > 0).sum())
+    if args.dump_outputs:   # the cold solve is the line's `value`
+        dump_outputs(args.dump_outputs, cold)
     # warm: the receding horizon, window s + 1 warm-started from window s
     bufs = [newbuf() for _ in range(S)]
     state = dict(xi=xi0.clone(), prev=None, s=0)
@@ -1007,6 +1064,8 @@ def receding_horizon(args, h, dev):
         step()
     torch.cuda.synchronize()
     sec = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs and state["s"]:   # the last timed window
+        dump_outputs(args.dump_outputs, bufs[state["s"] - 1])
     for _ in range(args.steps):
         step(timed=True)
     torch.cuda.synchronize()

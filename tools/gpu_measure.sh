@@ -2,8 +2,8 @@
 # One measurement session on the GPU box, every step under its own time limit, the first failure
 # ends it:  TAG=r06x tools/gpu_measure.sh [tests] [bench] [sqfbd] [ktrace_c5]
 #   tests      pytest -m gpu                         -> gpurun_out/$TAG_pytest_gpu.log
-#   bench      bench.py lines c2 (default), c5, mc, rh, c1, c3 (CPU baselines included)
-#                                                    -> gpurun_out/$TAG_bench_<w>.log
+#   bench      bench.py --full lines c2 (default), c5, mc, rh, c1, c3 (CPU baselines and roofline
+#              included)                             -> $OUT/$TAG_bench_<w>.log (OUT: measure_out)
 #   sqfbd      SQ counter passes of fbd_euler_kernel (tools/gpu_sq.sh, SQ_EXTRA=1) and their
 #              summary                              -> gpurun_out/$TAG_fbd_euler_sq.json
 #   ktrace_c5  rocprofv3 kernel trace + stats of the c5 bench -> gpurun_out/$TAG_ktrace_c5/
@@ -19,10 +19,11 @@ for step in "$@"; do
           -p no:cacheprovider > gpurun_out/${TAG}_pytest_gpu.log 2>&1
       rc=$?; tail -3 gpurun_out/${TAG}_pytest_gpu.log; [ $rc = 0 ] || { echo "tests rc=$rc"; exit $rc; } ;;
     bench)
+      OUT=${OUT:-measure_out}; mkdir -p "$OUT"
       for w in ${WORKLOADS:-c2 c5 mc rh c1 c3}; do
-        timeout -k 10 400 python -u bench.py --workload $w > gpurun_out/${TAG}_bench_$w.log 2>&1 \
-            || { echo "bench $w failed"; tail -5 gpurun_out/${TAG}_bench_$w.log; exit 1; }
-        echo "$w: $(grep -v amdgpu.ids gpurun_out/${TAG}_bench_$w.log | tail -1 | cut -c1-300)"
+        timeout -k 10 400 python -u bench.py --full --workload $w > $OUT/${TAG}_bench_$w.log 2>&1 \
+            || { echo "bench $w failed"; tail -5 $OUT/${TAG}_bench_$w.log; exit 1; }
+        echo "$w: $(grep -v amdgpu.ids $OUT/${TAG}_bench_$w.log | tail -1 | cut -c1-300)"
       done ;;
     sqfbd)
       rm -rf gpurun_out/sq
