@@ -29,7 +29,7 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_contact_model_eval", "blf_contact_point_wrench", "blf_fbk_dynamics",
             "blf_fbk_euler_integrate", "blf_fbd_dynamics", "blf_fbd_euler_integrate",
             "blf_fb_dcm", "blf_dcm_posture_reference", "blf_fbd_euler_integrate_impedance",
-            "blf_fb_frame_state"]
+            "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -197,6 +197,10 @@ def lib():
             ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
         L.blf_fb_frame_state.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), _i32,
                                          _vp, _i64, _vp, _vp, _vp]
+        L.blf_rls_advance.argtypes = [_vp, _i32, _i32, _f64, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
+                                      _i64, _vp]
+        L.blf_contact_rls_advance.argtypes = [_vp, _f64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp,
+                                              _i32, _vp, _vp, _i64, _vp]
         L.blf_dcm_mpc_flops_per_iter.restype = _f64
         L.blf_set_qp_launch_mode.argtypes = [_i32, _i32]
         for name in EXPORTED:
@@ -711,6 +715,53 @@ class Handle:
             _ptr(points, torch.float64, (B, Q, 2), "points"), Q, ctypes.c_void_p(f.data_ptr()),
             ctypes.c_void_p(t.data_ptr()), _stream(stream)))
         return f, t
+
+    # ---- Estimators::RecursiveLeastSquare, batched, in place on state / covariance ------------
+    def rls_advance(self, regressor, measurements, state, covariance, meas_cov, lam=1.0,
+                    stream=None):
+        """T steps of B recursive-least-squares filters (blf_rls_advance): regressor [T,B,m,n],
+        measurements [T,B,m] (or without the T axis: one step), state [B,n], covariance [B,n,n],
+        meas_cov [m] (shared) or [B,m].  Updates state and covariance in place, returns them."""
+        torch = _torch()
+        B, n = state.shape
+        if regressor.dim() == 3:
+            regressor, measurements = regressor.unsqueeze(0), measurements.unsqueeze(0)
+        T, m = regressor.shape[0], regressor.shape[2]
+        shared = meas_cov.dim() == 1
+        _check(lib().blf_rls_advance(
+            self._h, n, m, float(lam),
+            _ptr(meas_cov, torch.float64, (m,) if shared else (B, m), "meas_cov"),
+            1 if shared else 0, _ptr(regressor, torch.float64, (T, B, m, n), "regressor"),
+            _ptr(measurements, torch.float64, (T, B, m), "measurements"), T,
+            _ptr(state, torch.float64, (B, n), "state"),
+            _ptr(covariance, torch.float64, (B, n, n), "covariance"), B, _stream(stream)))
+        return state, covariance
+
+    def contact_rls_advance(self, geometry, twist, pose, null_pose, wrench, state, covariance,
+                            meas_cov, lam=1.0, stream=None):
+        """T identification steps of B contacts' (spring, damper) from measured wrenches
+        (blf_contact_rls_advance): geometry [2] or [B,2] = (length, width), twist [T,B,6], pose
+        [T,B,12], wrench [T,B,6] (or without the T axis), null_pose [B,12], state [B,2], covariance
+        [B,2,2], meas_cov [6] or [B,6].  Updates state and covariance in place, returns them."""
+        torch = _torch()
+        B = state.shape[0]
+        if twist.dim() == 2:
+            twist, pose, wrench = twist.unsqueeze(0), pose.unsqueeze(0), wrench.unsqueeze(0)
+        T = twist.shape[0]
+        shared_cov = meas_cov.dim() == 1
+        shared_geo = geometry.dim() == 1
+        _check(lib().blf_contact_rls_advance(
+            self._h, float(lam),
+            _ptr(meas_cov, torch.float64, (6,) if shared_cov else (B, 6), "meas_cov"),
+            1 if shared_cov else 0,
+            _ptr(geometry, torch.float64, (2,) if shared_geo else (B, 2), "geometry"),
+            1 if shared_geo else 0, _ptr(twist, torch.float64, (T, B, 6), "twist"),
+            _ptr(pose, torch.float64, (T, B, 12), "pose"),
+            _ptr(null_pose, torch.float64, (B, 12), "null_pose"),
+            _ptr(wrench, torch.float64, (T, B, 6), "wrench"), T,
+            _ptr(state, torch.float64, (B, 2), "state"),
+            _ptr(covariance, torch.float64, (B, 2, 2), "covariance"), B, _stream(stream)))
+        return state, covariance
 
     def fbk_dynamics(self, rho, rot, twist, joint_vel, stream=None):
         """FloatingBaseSystemKinematics::dynamics: rot [B,3,3], twist [B,6], joint_vel [B,n]."""

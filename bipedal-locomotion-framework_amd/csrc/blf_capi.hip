@@ -172,7 +172,7 @@ blf_status blf_step_schedule(double initial_time, double final_time, double dT, 
 #endif
 // The sources' hash (Makefile SRC_HASH) makes the loaded library traceable to the tree it was
 // built from (blf/native.py build_provenance).
-const char* blf_version(void) { return "blf-mi355x 0.2.0 (abi 2, gfx950, fp64, -ffp-contract=off) src " BLF_SRC_HASH; }
+const char* blf_version(void) { return "blf-mi355x 0.3.0 (abi 3, gfx950, fp64, -ffp-contract=off) src " BLF_SRC_HASH; }
 
 
 blf_status blf_set_qp_launch_mode(int32_t fuse_stage2, int32_t single_kernel)
@@ -564,6 +564,65 @@ blf_status blf_fbk_euler_integrate(blf_handle* handle, int32_t ndof, double rho,
     if (st != BLF_OK) return st;
     return launch_fbk_euler(ndof, rho, pos, rot, joints, twist, joint_vel, batch, iterations, dT,
                             dT_last, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// The checks blf_rls_advance and blf_contact_rls_advance share (before any device work).
+static blf_status check_rls(const char* fn, blf_handle* handle, double lambda, int32_t steps,
+                            int64_t batch)
+{
+    BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
+    BLF_REQUIRE(steps >= 1, "%s: steps=%d, must be >= 1", fn, steps);
+    BLF_REQUIRE(batch >= 0, "%s: negative batch", fn);
+    BLF_REQUIRE(std::isfinite(lambda) && lambda > 0.0, "%s: lambda=%g, must be finite and positive",
+                fn, lambda);
+    return BLF_OK;
+}
+
+extern "C" {
+
+blf_status blf_rls_advance(blf_handle* handle, int32_t n, int32_t m, double lambda,
+                           const double* meas_cov, int32_t shared_cov, const double* regressor,
+                           const double* measurements, int32_t steps, double* state,
+                           double* covariance, int64_t batch, void* stream)
+{
+    const blf_status st = check_rls("blf_rls_advance", handle, lambda, steps, batch);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(meas_cov != nullptr, "blf_rls_advance: null meas_cov");
+    BLF_REQUIRE(regressor != nullptr, "blf_rls_advance: null regressor");
+    BLF_REQUIRE(measurements != nullptr, "blf_rls_advance: null measurements");
+    BLF_REQUIRE(state != nullptr, "blf_rls_advance: null state");
+    BLF_REQUIRE(covariance != nullptr, "blf_rls_advance: null covariance");
+    if (n < 1 || n > BLF_RLS_MAX_STATE)
+        return set_error(BLF_ERR_UNSUPPORTED, "blf_rls_advance: n=%d outside [1, %d]", n,
+                         BLF_RLS_MAX_STATE);
+    if (m < 1 || m > BLF_RLS_MAX_MEAS)
+        return set_error(BLF_ERR_UNSUPPORTED, "blf_rls_advance: m=%d outside [1, %d]", m,
+                         BLF_RLS_MAX_MEAS);
+    return launch_rls_advance(n, m, lambda, meas_cov, shared_cov, regressor, measurements, steps,
+                              state, covariance, batch, (hipStream_t)stream);
+}
+
+blf_status blf_contact_rls_advance(blf_handle* handle, double lambda, const double* meas_cov,
+                                   int32_t shared_cov, const double* geometry,
+                                   int32_t shared_geometry, const double* twist, const double* pose,
+                                   const double* null_pose, const double* wrench, int32_t steps,
+                                   double* state, double* covariance, int64_t batch, void* stream)
+{
+    const blf_status st = check_rls("blf_contact_rls_advance", handle, lambda, steps, batch);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(meas_cov != nullptr, "blf_contact_rls_advance: null meas_cov");
+    BLF_REQUIRE(geometry != nullptr, "blf_contact_rls_advance: null geometry");
+    BLF_REQUIRE(twist != nullptr, "blf_contact_rls_advance: null twist");
+    BLF_REQUIRE(pose != nullptr, "blf_contact_rls_advance: null pose");
+    BLF_REQUIRE(null_pose != nullptr, "blf_contact_rls_advance: null null_pose");
+    BLF_REQUIRE(wrench != nullptr, "blf_contact_rls_advance: null wrench");
+    BLF_REQUIRE(state != nullptr, "blf_contact_rls_advance: null state");
+    BLF_REQUIRE(covariance != nullptr, "blf_contact_rls_advance: null covariance");
+    return launch_contact_rls(lambda, meas_cov, shared_cov, geometry, shared_geometry, twist, pose,
+                              null_pose, wrench, steps, state, covariance, batch,
+                              (hipStream_t)stream);
 }
 
 }  // extern "C"

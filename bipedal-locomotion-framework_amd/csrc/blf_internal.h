@@ -112,6 +112,14 @@ blf_status launch_contact_point(const double* prm, int shared, const double* twi
                                 const double* pose, const double* null_pose, int64_t batch,
                                 const double* points, int32_t Q, double* force, double* torque,
                                 hipStream_t s);
+blf_status launch_rls_advance(int n, int m, double lambda, const double* meas_cov, int shared_cov,
+                              const double* regressor, const double* meas, int32_t steps,
+                              double* state, double* cov, int64_t batch, hipStream_t s);
+blf_status launch_contact_rls(double lambda, const double* meas_cov, int shared_cov,
+                              const double* geometry, int shared_geometry, const double* twist,
+                              const double* pose, const double* null_pose, const double* wrench,
+                              int32_t steps, double* state, double* cov, int64_t batch,
+                              hipStream_t s);
 blf_status launch_fbk_dynamics(int n, double rho, const double* rot, const double* twist,
                                const double* joint_vel, double* dpos, double* drot,
                                double* djoints, int64_t batch, hipStream_t s);

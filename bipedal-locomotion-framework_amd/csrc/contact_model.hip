@@ -16,17 +16,6 @@
 namespace blf {
 namespace {
 
-// skew(e)^2 = e e^T - |e|^2 I, row-major
-__device__ __forceinline__ void skew2(V3 e, double* S)
-{
-    const double n = (e.x * e.x + e.y * e.y) + e.z * e.z;
-    const double ev[3] = {e.x, e.y, e.z};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) S[3 * i + j] = i == j ? ev[i] * ev[j] - n : ev[i] * ev[j];
-}
-
 // One wavefront per 64 contacts.  The tile's twist / pose / null-pose rows (6 + 12 + 12 doubles
 // per contact) arrive as coalesced 16-B loads, all three arrays' loads in flight together, into
 // one LDS slab (row stride 31); every lane then reads its own row.  Each requested output leaves
@@ -186,19 +175,7 @@ __global__ __launch_bounds__(kCT) void contact_eval_kernel(
         }
         if (regressor) {
             if (own) {
-                const double cf = aR * area;
-                const double cv = -aR * area;
-                const double ct = area / 12.0 * aR;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    o[2 * i] = cf * (p0v[i] - p[i]);
-                    o[2 * i + 1] = cv * v[i];
-                    o[2 * (3 + i)] = ct * (LL * at(t1, i) + WW * at(t2, i));
-                    const double M0 = LL * S1[3 * i] + WW * S2[3 * i];
-                    const double M1 = LL * S1[3 * i + 1] + WW * S2[3 * i + 1];
-                    const double M2 = LL * S1[3 * i + 2] + WW * S2[3 * i + 2];
-                    o[2 * (3 + i) + 1] = ct * ((M0 * w.x + M1 * w.y) + M2 * w.z);
-                }
+                contact_regressor_terms(aR, area, LL, WW, p0v, p, v, w, t1, t2, S1, S2, o);
             }
             flush(regressor, 12);
         }

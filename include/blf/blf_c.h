@@ -49,6 +49,11 @@
  *   blf_dcm_mpc_solve[_warm]  ABSENT in the reference (TimeVaryingDCMPlanner QP),
  *                             driven through System/Advanceable.h:24-46 (advance()) by the C++ host
  *                             adapter blf::Planners::TimeVaryingDCMPlanner
+ *   blf_rls_advance           Estimators/src/RecursiveLeastSquare.cpp:96-133
+ *                             (RecursiveLeastSquare::advance(), T steps of a batch of filters)
+ *   blf_contact_rls_advance   the same advance() with ContinuousContactModel::getRegressor()
+ *                             (ContinuousContactModel.cpp:223-254) as the regressor function: the
+ *                             online identification of a contact's spring and damper
  */
 #ifndef BLF_C_H
 #define BLF_C_H
@@ -86,13 +91,14 @@ blf_status blf_create(blf_handle** handle, int32_t device);
 blf_status blf_destroy(blf_handle* handle);
 /* Human-readable description of the last error on this thread (never NULL). */
 const char* blf_last_error(void);
-/* Version string of the library: "blf-mi355x <version> (abi <n>, ...) src <hash>".  ABI 2 (0.2.0)
- * added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
+/* Version string of the library: "blf-mi355x <version> (abi <n>, ...) src <hash>".  ABI 3 (0.3.0)
+ * is additive: it adds blf_rls_advance and blf_contact_rls_advance and changes no existing entry
+ * point or struct.  ABI 2 (0.2.0) added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
  * a caller built against an older header must zero-initialise these structs (`= {0}`), since the
  * library reads every field as a device pointer or NULL.  Solves that use a stream's stage-2 list
  * (blf_dcm_mpc_solve*) are refused with BLF_ERR_UNSUPPORTED while that stream is being captured
  * into a graph: the list's slot is sequenced on the host. */
-#define BLF_ABI_VERSION 2
+#define BLF_ABI_VERSION 3
 const char* blf_version(void);
 /* QP kernel routing for A/B and parity tests (no reference counterpart; the defaults are the
  * product's).  fuse_stage2 = 0: small cold batches with N <= 64 run the IPM's stage 2 as its own
@@ -556,6 +562,52 @@ blf_status blf_fbd_euler_integrate_impedance(blf_handle* handle, const blf_fb_mo
                                              const double* mass_reg, int64_t batch,
                                              double initial_time, double final_time, double dT,
                                              void* stream);
+/* ---- 10. Recursive least squares (Estimators::RecursiveLeastSquare), batched ------------------
+ * B independent filters, each with state x (n), covariance P (n x n), forgetting factor lambda and
+ * a diagonal measurement covariance R = diag(r) (m).  One step with regressor H (m x n) and
+ * measurements y (m) is the reference's advance() (RecursiveLeastSquare.cpp:119-130):
+ *   K = P H^T (lambda R + H P H^T)^-1;  x <- x + K (y - H x);  P <- (P - K H P) / lambda.
+ * R is diagonal, so the step is evaluated as m sequential scalar updates and one division (the
+ * same minimiser and the same P in exact arithmetic, P+ = (lambda P^-1 + H^T R^-1 H)^-1; no m x m
+ * inverse).  Only the upper triangle of P is kept: the input covariance is read through its upper
+ * triangle and the output is mirrored, so it is exactly symmetric.
+ * Arithmetic order (no FMA contraction; every sum left to right, starting from its first term).
+ * For each row j = 0..m-1 of H, h = H[j][:]:
+ *   g_a = sum_c P[a][c] h_c                       (P[a][c] = P[c][a] for a > c)
+ *   s   = (lambda * r_j) + sum_a h_a g_a
+ *   e   = y_j - sum_a h_a x_a
+ *   k_a = g_a / s
+ *   x_a = x_a + k_a * e
+ *   P[a][b] = P[a][b] - k_a * g_b                 (a <= b)
+ * and after the m rows P[a][b] = P[a][b] / lambda.  If s is not a finite positive number (NaN, <=
+ * 0 or +inf: e.g. r_j = 0 with a zero row), every element of that filter's x and P becomes NaN at
+ * that row and stays NaN; other filters are unaffected.
+ * Samples are STEP-MAJOR: regressor [T][B][m][n], measurements [T][B][m] (each step one contiguous
+ * batch array, what blf_contact_model_eval produces per period; a closed loop calls with
+ * steps = 1).  meas_cov: [m] when shared_cov != 0, else [B][m].  state [B][n] and covariance
+ * [B][n][n] (row-major) are updated in place.  Errors: null handle or pointer, steps < 1,
+ * batch < 0, lambda not finite or not positive: BLF_ERR_INVALID_ARGUMENT; n outside
+ * 1..BLF_RLS_MAX_STATE or m outside 1..BLF_RLS_MAX_MEAS: BLF_ERR_UNSUPPORTED; batch == 0: BLF_OK. */
+#define BLF_RLS_MAX_STATE 8
+#define BLF_RLS_MAX_MEAS  8
+blf_status blf_rls_advance(blf_handle* handle, int32_t n, int32_t m, double lambda,
+                           const double* meas_cov, int32_t shared_cov, const double* regressor,
+                           const double* measurements, int32_t steps, double* state,
+                           double* covariance, int64_t batch, void* stream);
+
+/* The identification of a ContinuousContactModel's (spring_coeff, damper_coeff) from measured
+ * wrenches: blf_rls_advance with n = 2, m = 6, whose regressor of step t is
+ * blf_contact_model_eval's `regressor` output for (geometry, twist[t], pose[t], null_pose), formed
+ * on chip (bit-identical to the two calls in sequence).  geometry: {length, width}, [2] when
+ * shared_geometry != 0, else [B][2]; meas_cov: [6] or [B][6]; twist [T][B][6], pose [T][B][12],
+ * null_pose [B][12], wrench [T][B][6] (the measurements); state [B][2] = (k, b) and covariance
+ * [B][2][2] in place.  Errors as blf_rls_advance. */
+blf_status blf_contact_rls_advance(blf_handle* handle, double lambda, const double* meas_cov,
+                                   int32_t shared_cov, const double* geometry,
+                                   int32_t shared_geometry, const double* twist, const double* pose,
+                                   const double* null_pose, const double* wrench, int32_t steps,
+                                   double* state, double* covariance, int64_t batch, void* stream);
+
 /* Algorithmic flop count of one IPM iteration of one problem (what the fp64 roofline field
  * of bench.py is computed from); `active_facets` = sum_k nfacets[k]. */
 double blf_dcm_mpc_flops_per_iter(int32_t horizon, int64_t active_facets);
