@@ -16,15 +16,21 @@
 //           the origin),
 // which is exactly sum_l m Jv^T Jv + Jw^T I Jw, h and J_c^T w_c of the Jacobian form
 // (oracle/fb_dynamics.py evaluates that form; the two agree to rounding).
-// One 64-lane workgroup (one wavefront) per system, everything in LDS:
+// One 64-lane workgroup (one wavefront) per system, or per two systems of at most 32 rows (struct
+// Half), everything in LDS:
 //   1. per-joint rotations, lane per joint;  2. forward kinematics by pointer jumping along the
-//   ancestor chains (every joint lane at once, log2 of the depth rounds);  3. per-link spatial inertia / force, lane per link;
-//   4. contact wrenches, lane per contact;  5. subtree sums, lane per (subtree, parameter), the
-//   ancestor bitmask of each link selecting the members;  6. column axes, their composite products
-//   and the right-hand side, lane per column;  7. M, lane per lower-triangle entry;  8. Cholesky,
-//   left-looking with one lane per row (one barrier per column);  9. forward and back
-//   substitution with the right-hand side in registers (lane per row, pivots broadcast by
-//   v_readlane, reciprocal pivots precomputed).
+//   ancestor chains (every joint lane at once, log2 of the depth rounds);  4. contact wrenches,
+//   lane per contact (they run before step 3);  3. per-link spatial inertia / force with the
+//   link's contact wrenches subtracted, lane per link.
+// From there the default is the articulated-body solve (fbd_aba): one inward and one outward
+// sweep over the tree levels, no mass matrix.  A model with a mass-matrix regularisation
+// (mass_reg != NULL), which needs M itself, takes steps 5-9 instead:
+//   5. subtree sums: a DPP prefix sum per component over DFS-ordered joints, otherwise level by
+//   level from the leaves;  6. column axes, their composite products and the right-hand side, lane
+//   per column;  7. M, lane per row (the row in registers);  8. Cholesky, right-looking, two
+//   columns per step, lane per row, the pivot columns through LDS behind a wavefront fence (no
+//   s_barrier);  9. forward and back substitution with the right-hand side in registers (lane per
+//   row, the unknowns broadcast by v_readlane).
 #include "blf_internal.h"
 #include "contact_math.h"
 #include "dcm_qp_common.h"   // the DPP prefix-scan levels (qp::tree_fwd / tree_has)
@@ -71,54 +77,9 @@ __device__ __forceinline__ void wave_sync()
 // an ODD number of doubles: consecutive lanes then fall on distinct LDS bank pairs and an 8-byte
 // access of 32 lanes is conflict-free.  With the even strides of the data sizes (40, 16, 12, 6
 // doubles) SQ_LDS_BANK_CONFLICT was 83k quad-cycles per wave, 16 % of the Euler kernel's cycles
-// (profiles/r03_fbd_euler_sq.json); BLF_FBD_PAD=0 builds the old layout for A/B.
-#ifndef BLF_FBD_PAD
-#define BLF_FBD_PAD 1
-#endif
-#ifndef BLF_FBD_CHOLB
-#define BLF_FBD_CHOLB 2
-#endif
-// the Euler kernel's substitutions (fbd_eval FOLD): 0 two loops after the factorization, 1 the
-// forward one inside it, 2 that and L stored column-major by the factorization itself.  Measured
-// (profiles/r04_fbd_fold_ab.log, one c5 period of fbd_euler_kernel, two rounds on one box): 1 took
-// 4.747 / 4.740 ms against 4.701 / 4.705 ms for 0 (the block's y broadcasts lengthen every
-// factorization step's chain more than the separate loop costs); 2 spills 318 VGPRs.  So 0.
-#ifndef BLF_FBD_SCANX   // the subtree sums' gathers: 1 = one ds_bpermute per component (0: three, A/B)
-#define BLF_FBD_SCANX 1   // 4.657 / 4.640 against 4.671 / 4.656 ms per c5 period (profiles/r04_fbd_scanx_ab.log)
-#endif
-#ifndef BLF_FBD_LDSMODEL   // fbd_euler_kernel reads the model's constants from an LDS copy (A/B)
-#define BLF_FBD_LDSMODEL 0   // 1: 5.92 / 5.93 against 4.24 / 4.24 ms per c5 period (profiles/r04_fbd_kinjump_ab.log)
-#endif
-#ifndef BLF_FBD_FOLD
-#define BLF_FBD_FOLD 0
-#endif
-#ifndef BLF_FBD_PREFIX_LDS   // DFS subtree sums: step 5 leaves the prefix sums, step 6 takes the differences (1)
-#define BLF_FBD_PREFIX_LDS 1   // or step 5 gathers them by lane shuffles (0, A/B): 3.812 / 3.811 against
-                               // 4.077 / 4.074 ms per c5 period (profiles/r04_fbd_prefix_opq_ab.log)
-#endif
-#ifndef BLF_FBD_SUBST   // substitutions with the pivot scaling on the multipliers (1, A/B) or on the unknowns (0)
-#define BLF_FBD_SUBST 0   // 1: 3.914 / 3.904 against 3.792 / 3.792 ms per c5 period (profiles/r04_fbd_subst_ab.log)
-#endif
-#ifndef BLF_FBD_KINJUMP   // steps 1-2 by pointer jumping (1) or tree level by level (0, A/B)
-#define BLF_FBD_KINJUMP 1     // 4.238 / 4.239 against 4.688 / 4.704 ms per c5 period of fbd_euler_kernel
-#endif                        // (profiles/r04_fbd_kinjump_ab.log); 15.3k -> 9.3k cycles per evaluation
-#ifndef BLF_FBD_CSTAGE   // fbd_euler_kernel stages each system's contact / impedance constants in LDS (1) or
-#define BLF_FBD_CSTAGE 1   // reads them from global memory every Euler step (0, A/B): 3.793 / 3.773 against
-                           // 3.805 / 3.785 ms per c5 period (profiles/r04_cstage_asopq_ab.log)
-#endif
-#ifndef BLF_FBD_COLFIX   // the factorization's column sets at a compile-time stride (1, A/B) or at NV (0)
-#define BLF_FBD_COLFIX 0   // 1: Cholesky 19.9k -> 14.8k cycles in fbd_dynamics_kernel, but one c5 period of the
-#endif                     // Euler kernel 4.04 / 4.02 against 3.77 / 3.76 ms (profiles/r04_fbd_colfix_cstage_ab.log)
-#ifndef BLF_FBD_OPQLANE   // fbd_eval's lane index opaque per evaluation (1) or not (0, A/B)
-#define BLF_FBD_OPQLANE 1   // 3.812 / 3.811 against 3.856 / 3.860 ms per c5 period; SGPR spills 595 -> 366,
-#endif                      // VGPR spills 17 -> 0 (profiles/r04_fbd_prefix_opq_ab.log)
-#ifndef BLF_FBD_CSUB   // contact wrenches subtracted from the link forces in step 3 (1) or in step 5 (0, A/B)
-#define BLF_FBD_CSUB 1  // 4.070 / 4.078 against 4.198 / 4.200 ms per c5 period (profiles/r04_fbd_csub_ab.log)
-#endif
+// (profiles/r03_fbd_euler_sq.json).
+constexpr int kPad = 1;
 
-constexpr int kPad = BLF_FBD_PAD;
-constexpr bool kPrefixLds = BLF_FBD_PREFIX_LDS && BLF_FBD_CSUB;   // (the base's contacts: step 3)
-constexpr bool kSubst = BLF_FBD_SUBST && BLF_FBD_CHOLB > 1;        // (the pivots: the block factorization)
 constexpr int kLinkRec = 40 + kPad;   // record stride (40 doubles of data)
 constexpr int kR = 0, kP = 9, kW = 12, kV = 15, kAl = 18, kA = 21, kSI = 24, kSF = 34;
 // The articulated-body layout (Smem aba): 27-double records.  Step 3 writes a link's spatial
@@ -131,14 +92,13 @@ constexpr int kSIa = 0, kSFa = 10;
 constexpr int kComp = 16;             // subtree sum: spatial inertia 10 | spatial force 6
 constexpr int kCompS = kComp + kPad;  // its stride
 constexpr int kCs = 16 + kPad;        // contact scratch: point 3 | wrench 6 | link 1 | spatial wrench 6
-constexpr int kJrot = 12 + kPad;      // per-joint E_j Rot (9) | E_j a_j (3)
 constexpr int kSax = 6 + kPad;        // column axis (w, u)
 
 struct Smem {
     // one base pointer (per system: the two halves of a wavefront have their own) and wave-uniform
     // offsets, so the per-half base costs one address, not one per array
     double* base;
-    int o_link, o_jrot, o_jz, o_jo, o_comp, o_sax, o_rhs, o_cscr, o_st, o_tq, o_anc, o_cst, o_imp;
+    int o_link, o_jz, o_jo, o_comp, o_sax, o_rhs, o_cscr, o_st, o_tq, o_anc, o_cst, o_imp;
     int ms;   // row stride of L (odd: the per-lane row accesses do not conflict)
     int lrec;   // link record stride: kLinkRec, or kLinkRecA for the articulated-body solve
     size_t total;
@@ -160,13 +120,12 @@ struct Smem {
         // link records; after the mass matrix is assembled the same space holds L (NV rows)
         const size_t lk = (size_t)lrec * L, lm = aba ? 0 : (size_t)NV * ms;
         o_link = take(lk > lm ? lk : lm);
-        o_jrot = take(BLF_FBD_KINJUMP ? 0 : kJrot * (size_t)n);   // E_j Rot(a_j, s_j) (9) | E_j a_j (3): levels only
         o_jz = take(3 * (size_t)n);
         o_jo = take(3 * (size_t)n);
         // subtree sums [j] (joint j's subtree) and [n] (every link); later the pivot-column
         // buffers of the factorization (two sets of up to 4 columns, 8 NV)
         const size_t cp = (size_t)kCompS * (n + 1);
-        const size_t cb = 8 * (size_t)(NV > 32 ? NV : 32);   // (BLF_FBD_COLFIX: 2 CB NVMAX)
+        const size_t cb = 8 * (size_t)(NV > 32 ? NV : 32);
         o_comp = take(aba ? 0 : cp > cb ? cp : cb);
         o_sax = take(aba ? 0 : kSax * (size_t)NV);
         o_rhs = take((size_t)NV);
@@ -174,14 +133,15 @@ struct Smem {
         o_st = take(18 + 2 * (size_t)n + (size_t)NV + 9);   // Euler state (6 + n + 3 + 9 + n) + acc + dR
         o_tq = take((size_t)n);                              // the joint impedance's torques
         o_anc = take((size_t)L);
-        // fbd_euler_kernel's per-system constants (BLF_FBD_CSTAGE): each contact's link, frame
-        // pose, null pose and parameters [C | 12 C | 12 C | 4 C]; the impedance's kp, kd, q_ref
-        o_cst = take(BLF_FBD_CSTAGE ? 29 * (size_t)C : 0);
-        o_imp = take(BLF_FBD_CSTAGE ? 3 * (size_t)n : 0);
+        // fbd_euler_kernel's per-system constants, staged once instead of read from global memory
+        // every Euler step: each contact's link, frame pose, null pose and parameters
+        // [C | 12 C | 12 C | 4 C]; the impedance's kp, kd, q_ref (3.793 / 3.773 against 3.805 /
+        // 3.785 ms per c5 period, profiles/r04_cstage_asopq_ab.log)
+        o_cst = take(29 * (size_t)C);
+        o_imp = take(3 * (size_t)n);
         total = o;
     }
     __device__ __forceinline__ double* link() const { return base + o_link; }
-    __device__ __forceinline__ double* jrot() const { return base + o_jrot; }
     __device__ __forceinline__ double* jz() const { return base + o_jz; }
     __device__ __forceinline__ double* jo() const { return base + o_jo; }
     __device__ __forceinline__ double* comp() const { return base + o_comp; }
@@ -198,15 +158,6 @@ struct Smem {
     }
 };
 
-// doubles of fbd_euler_kernel's LDS model block (BLF_FBD_LDSMODEL)
-template <int NVMAX>
-__host__ __device__ constexpr int fbd_model_block()
-{
-    // rounded up to an even count: the halves' state blocks after it stay 16-B aligned
-    return (3 * (NVMAX - 6) + 9 * (NVMAX - 6) + 3 * (NVMAX - 5) + 9 * (NVMAX - 5) + (NVMAX - 5) + 2 * (NVMAX - 6) +
-            13 * BLF_FBD_MAX_CONTACTS + 1) & ~1;
-}
-
 struct Model {
     int n, F;
     const int32_t* parent;
@@ -214,8 +165,7 @@ struct Model {
     const int32_t* flink;
     double g0, g1, g2, rho;
     const int32_t* jtype;   // [n] or nullptr: BLF_JOINT_PRISMATIC marks a sliding joint
-    // fbd_euler_kernel's LDS copy (BLF_FBD_LDSMODEL): each contact's frame pose [C][12] and link
-    // [C] (read through these when fbd_eval's LM is set)
+    // unused (always null): dropping them moves the register allocation of the prismatic Euler kernels
     const double* cpose;
     const double* clink;
 };
@@ -231,12 +181,9 @@ struct Contacts {
 
 // Whether contact c applies the caller's wrench (BLF_CONTACT_WRENCH) instead of the
 // ContinuousContactModel law
-#ifndef BLF_FBD_LAWS   // 0: the continuous law only (A/B of the law branch, tools/gpu_r05i.sh)
-#define BLF_FBD_LAWS 1
-#endif
 __device__ __forceinline__ bool given_wrench(const Contacts& ct, int c)
 {
-    return BLF_FBD_LAWS && ct.law != nullptr && ct.law[c] == BLF_CONTACT_WRENCH;
+    return ct.law != nullptr && ct.law[c] == BLF_CONTACT_WRENCH;
 }
 
 __device__ __forceinline__ void cross3(const double* a, const double* b, double* o)
@@ -376,115 +323,6 @@ __device__ __forceinline__ Topo build_topo(const Model& m, const Smem& S)
     return t;
 }
 
-// Steps 1-2 of fbd_eval: per-joint rotations and forward kinematics (poses, mixed velocities,
-// nu_dot = 0 accelerations) of every link into the link records.
-// PRI: the model may hold prismatic joints (blf_fb_model.joint_type != NULL); the launchers
-// instantiate the kernels both ways, so all-revolute models (config 5) pay nothing for it.
-template <int HW, bool PRI>
-__device__ __forceinline__ void fbd_kinematics_levels(const Model& m, const Smem& S, const double* bv,
-                                                      const double* jvel, const double* bp, const double* bR,
-                                                      const double* jp, const Topo& T)
-{
-    const int n = m.n;
-    const int lane = Half<HW>().hl;
-    const bool jl = lane < n;   // n <= 48 < 64: one joint per lane
-    const int depth = T.depth, P = T.P, maxdepth = T.maxdepth;
-    const double sd = jl ? jvel[lane] : 0.0;
-    // 1. per-joint rotation E_j Rot(a_j, s_j) (Rodrigues) and E_j a_j, lane per joint
-    if (jl) {
-        const int j = lane;
-        const double* a = m.jaxis + 3 * j;
-        const double* E = m.jrot + 9 * j;
-        double sn = 0.0, cs = 1.0;   // a prismatic joint does not rotate: E Rot(a, 0) = E exactly
-        if (!(PRI && m.jtype[j] == BLF_JOINT_PRISMATIC)) sincos(jp[j], &sn, &cs);
-        if (PRI && m.jtype[j] != BLF_JOINT_PRISMATIC && m.jtype[j] != BLF_JOINT_REVOLUTE)
-            sn = cs = __builtin_nan("");   // an unknown joint type: the robot's outputs are NaN
-        const double c1 = 1.0 - cs;
-        const double K[9] = {0.0, -a[2], a[1], a[2], 0.0, -a[0], -a[1], a[0], 0.0};
-        double Rr[9];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double K2 = (K[3 * r] * K[c] + K[3 * r + 1] * K[3 + c]) + K[3 * r + 2] * K[6 + c];
-                Rr[3 * r + c] = ((r == c ? 1.0 : 0.0) + sn * K[3 * r + c]) + c1 * K2;
-            }
-        double* out = S.jrot() + kJrot * j;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                out[3 * r + c] = (E[3 * r] * Rr[c] + E[3 * r + 1] * Rr[3 + c]) + E[3 * r + 2] * Rr[6 + c];
-            out[9 + r] = (E[3 * r] * a[0] + E[3 * r + 1] * a[1]) + E[3 * r + 2] * a[2];
-        }
-    }
-    if (lane == 0) {
-        double* b = S.link();
-        for (int i = 0; i < 9; ++i) b[kR + i] = bR[i];
-        for (int i = 0; i < 3; ++i) {
-            b[kP + i] = bp[i]; b[kV + i] = bv[i]; b[kW + i] = bv[3 + i];
-            b[kAl + i] = 0.0; b[kA + i] = 0.0;
-        }
-    }
-    wave_sync();
-    // 2. forward kinematics, one tree level at a time: poses, mixed velocities, nu_dot = 0
-    //    accelerations of every joint whose parent link is done
-    for (int lev = 0; lev <= maxdepth; ++lev) {
-        if (jl && depth == lev) {
-            const int j = lane;
-            // the parent link's record and this joint's rotation into registers first (the child
-            // record's stores could otherwise alias them and delay the loads)
-            double pr[24], Ej[12];
-            const double* prs = S.link() + S.lrec * P;
-#pragma unroll
-            for (int i = 0; i < 24; ++i) pr[i] = prs[i];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) Ej[i] = S.jrot()[kJrot * j + i];
-            const double o[3] = {T.o0, T.o1, T.o2};
-            const double* RP = pr + kR;
-            double cR[9], r[3], z[3];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    cR[3 * a + c] = (RP[3 * a] * Ej[c] + RP[3 * a + 1] * Ej[3 + c]) + RP[3 * a + 2] * Ej[6 + c];
-                r[a] = (RP[3 * a] * o[0] + RP[3 * a + 1] * o[1]) + RP[3 * a + 2] * o[2];
-                z[a] = (RP[3 * a] * Ej[9] + RP[3 * a + 1] * Ej[10]) + RP[3 * a + 2] * Ej[11];
-            }
-            const double zs[3] = {z[0] * sd, z[1] * sd, z[2] * sd};
-            // prismatic (oracle/fb_dynamics.py): r = R_P o + z q, w_c = w_P, al_c = al_P,
-            // v_c = v_P + w_P x r + z sd, a_c = a_P + al_P x r + w_P x (w_P x r) + 2 w_P x z sd
-            const bool pri = PRI && m.jtype[j] == BLF_JOINT_PRISMATIC;
-            if (pri) {
-                const double qj = jp[j];
-#pragma unroll
-                for (int a = 0; a < 3; ++a) r[a] = r[a] + z[a] * qj;
-            }
-            double t1[3], t2[3], t3[3], t4[3];
-            cross3(pr + kW, r, t1);            // w_P x r
-            cross3(pr + kW, zs, t2);           // w_P x z sd
-            cross3(pr + kAl, r, t3);           // al_P x r
-            cross3(pr + kW, t1, t4);           // w_P x (w_P x r)
-            double* cr = S.link() + S.lrec * (j + 1);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) cr[kR + i] = cR[i];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double pc = pr[kP + a] + r[a];
-                cr[kP + a] = pc;
-                S.jz()[3 * j + a] = z[a];
-                S.jo()[3 * j + a] = pc;
-                const double arev = (pr[kA + a] + t3[a]) + t4[a];
-                cr[kW + a] = pri ? pr[kW + a] : pr[kW + a] + zs[a];
-                cr[kV + a] = pri ? (pr[kV + a] + t1[a]) + zs[a] : pr[kV + a] + t1[a];
-                cr[kAl + a] = pri ? pr[kAl + a] : pr[kAl + a] + t2[a];
-                cr[kA + a] = pri ? arev + 2.0 * t2[a] : arev;
-            }
-        }
-        wave_sync();
-    }
-}
-
 // motion cross product (w, v) x (w2, v2) = (w x w2, w x v2 + v x w2), accumulated into o
 __device__ __forceinline__ void crm_add(const double* s, const double* t, double* o)
 {
@@ -499,8 +337,14 @@ __device__ __forceinline__ void crm_add(const double* s, const double* t, double
     }
 }
 
-// Steps 1-2 by pointer jumping along the ancestor chains (BLF_FBD_KINJUMP): every joint lane runs
-// at once, and a chain of depth D takes ceil(log2(D + 1)) rounds instead of D + 1 tree levels.
+// Steps 1-2 of fbd_eval: per-joint rotations and forward kinematics (poses, mixed velocities,
+// nu_dot = 0 accelerations) of every link into the link records.
+// PRI: the model may hold prismatic joints (blf_fb_model.joint_type != NULL); the launchers
+// instantiate the kernels both ways, so all-revolute models (config 5) pay nothing for it.
+// By pointer jumping along the ancestor chains: every joint lane runs at once, and a chain of
+// depth D takes ceil(log2(D + 1)) rounds instead of D + 1 tree levels (4.238 / 4.239 against
+// 4.688 / 4.704 ms per c5 period of fbd_euler_kernel, 15.3k -> 9.3k cycles per evaluation;
+// profiles/r04_fbd_kinjump_ab.log).
 //  * Poses: lane j holds the transform (R, p) from link ptr (initially its parent; the base's
 //    world pose is folded in at once where the parent is the base, ptr = 0 then means "anchored in
 //    the world") to its link j + 1.  A round composes the record of link ptr -- the segment from
@@ -514,11 +358,11 @@ __device__ __forceinline__ void crm_add(const double* s, const double* t, double
 //    (w_B, v_B + p_B x w_B), A_B = (0, -(w_B x v_B)): the base's nu_dot = 0).
 // A lane reads its partner's record before it writes its own in the same round: the wavefront's
 // LDS operations complete in program order, so every read sees the previous round's values.
-// Rounding differs from the level recursion (parity is the 1e-9 bar of the fb tests).
+// Rounding differs from a level-by-level recursion (parity is the 1e-9 bar of the fb tests).
 template <int HW, bool PRI>
-__device__ __forceinline__ void fbd_kinematics_jump(const Model& m, const Smem& S, const double* bv,
-                                                    const double* jvel, const double* bp, const double* bR,
-                                                    const double* jp, const Topo& T)
+__device__ __forceinline__ void fbd_kinematics(const Model& m, const Smem& S, const double* bv,
+                                               const double* jvel, const double* bp, const double* bR,
+                                               const double* jp, const Topo& T)
 {
     const Half<HW> H;
     const int n = m.n;
@@ -717,16 +561,6 @@ __device__ __forceinline__ void fbd_kinematics_jump(const Model& m, const Smem& 
         }
     }
     wave_sync();
-}
-
-
-template <int HW, bool PRI>
-__device__ __forceinline__ void fbd_kinematics(const Model& m, const Smem& S, const double* bv,
-                                               const double* jvel, const double* bp, const double* bR,
-                                               const double* jp, const Topo& T)
-{
-    if constexpr (BLF_FBD_KINJUMP) fbd_kinematics_jump<HW, PRI>(m, S, bv, jvel, bp, bR, jp, T);
-    else fbd_kinematics_levels<HW, PRI>(m, S, bv, jvel, bp, bR, jp, T);
 }
 
 // ---- The articulated-body solve (round 5): nu_dot without M, its factorization or the
@@ -946,7 +780,7 @@ __device__ __forceinline__ void frame_state(const double* k, const double* fp, d
 // NVMAX >= n + 6 bounds the unrolled factorization loops (each lane keeps its row of M in
 // registers).  Lane j < n owns joint j in steps 1, 2 and 5; lane i < NV owns row / column i in
 // steps 6-9.
-template <int NVMAX, int HW, bool PRI, int FOLD = 0, bool LM = false, bool CS = false, bool ABA = false>
+template <int NVMAX, int HW, bool PRI, bool CS, bool ABA>
 __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const double* bv,
                                          const double* jvel, const double* bp, const double* bR,
                                          const double* jp, const double* tau, const Contacts& ct,
@@ -955,22 +789,61 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
     static_assert(NVMAX <= HW, "a system's rows must fit its lanes");
     const Half<HW> H;
     const int n = m.n, L = n + 1, NV = n + 6, MS = S.ms;
-    // BLF_FBD_OPQLANE: the lane index made opaque once per evaluation, so the lane masks of the
-    // unrolled loops (lane == k, lane > k, ...) are recomputed by one compare each instead of being
-    // hoisted out of the Euler loop into SGPRs, which spill to VGPR lanes and reload by v_readlane
+    // The lane index made opaque once per evaluation, so the lane masks of the unrolled loops
+    // (lane == k, lane > k, ...) are recomputed by one compare each instead of being hoisted out of
+    // the Euler loop into SGPRs, which spill to VGPR lanes and reload by v_readlane: 3.812 / 3.811
+    // against 3.856 / 3.860 ms per c5 period, SGPR spills 595 -> 366, VGPR spills 17 -> 0
+    // (profiles/r04_fbd_prefix_opq_ab.log)
     int lane = H.hl;
-    if constexpr (BLF_FBD_OPQLANE) asm volatile("" : "+v"(lane));
+    asm volatile("" : "+v"(lane));
     const bool jl = lane < n;   // n <= 48 < 64: one joint per lane
     const int depth = T.depth, maxdepth = T.maxdepth;
     FSTAMP(f_t0);
     FSTAMP(f_t1);
     fbd_kinematics<HW, PRI>(m, S, bv, jvel, bp, bR, jp, T);
     FSTAMP_ADD(1, f_t1);
-    FSTAMP(f_t2);
+    // 4. contacts: frame state + ContinuousContactModel wrench, and the wrench about the origin.
+    //    Before step 3, which needs the wrenches and overwrites the kinematics in the ABA layout.
+    FSTAMP(f_t3);
+    for (int c = lane; c < ct.C; c += HW) {
+        int l;
+        const double* fp;
+        if constexpr (CS) {
+            l = (int)S.cst()[c];
+            fp = S.cst() + ct.C + 12 * c;
+        } else {
+            const int f = ct.frame[c];
+            l = m.flink[f];
+            fp = m.fpose + 12 * f;
+        }
+        double pose[12], tw[6];
+        frame_state(S.link() + S.lrec * l, fp, pose, tw);
+        double* sc = S.cscr() + kCs * c;
+        if (given_wrench(ct, c)) {   // any ContactModel, evaluated by the caller
+            const double* gw = ct.wrench + (sys * ct.C + c) * 6;
+            for (int a = 0; a < 6; ++a) sc[3 + a] = gw[a];
+        } else if constexpr (CS)
+            contact_wrench(S.cst() + 25 * ct.C + 4 * c, tw, pose, S.cst() + 13 * ct.C + 12 * c, sc + 3);
+        else
+            contact_wrench(ct.params + 4 * c, tw, pose, ct.null_pose + (sys * ct.C + c) * 12, sc + 3);
+        sc[0] = pose[0]; sc[1] = pose[1]; sc[2] = pose[2];
+        sc[9] = (double)l;
+        double xf[3];
+        cross3(sc, sc + 3, xf);   // x_c x f_c
+        for (int a = 0; a < 3; ++a) {
+            sc[10 + a] = sc[6 + a] + xf[a];
+            sc[13 + a] = sc[3 + a];
+        }
+    }
+    wave_sync();
+    FSTAMP_ADD(3, f_t3);
     // 3. per link: COM, world inertia, Newton-Euler force / moment, and the spatial inertia and
-    //    force about the world origin (lane per link); BLF_FBD_CSUB: after step 4, with the
-    //    contact wrenches on the link (about the origin) subtracted from its force here, once,
-    //    instead of in every component group of the subtree sums
+    //    force about the world origin (lane per link), with the contact wrenches on the link
+    //    (about the origin) subtracted from its force here, once, instead of in every component
+    //    group of the subtree sums: 4.070 / 4.078 against 4.198 / 4.200 ms per c5 period
+    //    (profiles/r04_fbd_csub_ab.log)
+    // (a lambda with one call: written as a plain block the same arithmetic compiles with some
+    // commutative operands swapped, and this file's refactors are checked by identical assembly)
     auto link_step = [&]() {
     for (int l = lane; l < L; l += HW) {
         double* k = S.link() + S.lrec * l;
@@ -1020,74 +893,23 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
             sfv[a] = tq[a] + cf[a];
             sfv[3 + a] = f[a];
         }
-        if constexpr (BLF_FBD_CSUB) {
-            for (int cc2 = 0; cc2 < ct.C; ++cc2) {   // branch-free: the loads do not wait for the test
-                const double* sc = S.cscr() + kCs * cc2;
-                const bool hit = (int)sc[9] == l;
-                double w[6];
+        for (int cc2 = 0; cc2 < ct.C; ++cc2) {   // branch-free: the loads do not wait for the test
+            const double* sc = S.cscr() + kCs * cc2;
+            const bool hit = (int)sc[9] == l;
+            double w[6];
 #pragma unroll
-                for (int a = 0; a < 6; ++a) w[a] = sc[10 + a];
+            for (int a = 0; a < 6; ++a) w[a] = sc[10 + a];
 #pragma unroll
-                for (int a = 0; a < 6; ++a) sfv[a] = hit ? sfv[a] - w[a] : sfv[a];
-            }
+            for (int a = 0; a < 6; ++a) sfv[a] = hit ? sfv[a] - w[a] : sfv[a];
         }
         double* sf = k + (ABA ? kSFa : kSF);
         for (int a = 0; a < 6; ++a) sf[a] = sfv[a];
     }
     };
-    // 4. contacts: frame state + ContinuousContactModel wrench, and the wrench about the origin
-    auto contacts_step = [&]() {
-    for (int c = lane; c < ct.C; c += HW) {
-        int l;
-        const double* fp;
-        if constexpr (CS) {
-            l = (int)S.cst()[c];
-            fp = S.cst() + ct.C + 12 * c;
-        } else if constexpr (LM) {
-            l = (int)m.clink[c];
-            fp = m.cpose + 12 * c;
-        } else {
-            const int f = ct.frame[c];
-            l = m.flink[f];
-            fp = m.fpose + 12 * f;
-        }
-        double pose[12], tw[6];
-        frame_state(S.link() + S.lrec * l, fp, pose, tw);
-        double* sc = S.cscr() + kCs * c;
-        if (given_wrench(ct, c)) {   // any ContactModel, evaluated by the caller
-            const double* gw = ct.wrench + (sys * ct.C + c) * 6;
-            for (int a = 0; a < 6; ++a) sc[3 + a] = gw[a];
-        } else if constexpr (CS)
-            contact_wrench(S.cst() + 25 * ct.C + 4 * c, tw, pose, S.cst() + 13 * ct.C + 12 * c, sc + 3);
-        else
-            contact_wrench(ct.params + 4 * c, tw, pose, ct.null_pose + (sys * ct.C + c) * 12, sc + 3);
-        sc[0] = pose[0]; sc[1] = pose[1]; sc[2] = pose[2];
-        sc[9] = (double)l;
-        double xf[3];
-        cross3(sc, sc + 3, xf);   // x_c x f_c
-        for (int a = 0; a < 3; ++a) {
-            sc[10 + a] = sc[6 + a] + xf[a];
-            sc[13 + a] = sc[3 + a];
-        }
-    }
+    FSTAMP(f_t2);
+    link_step();
     wave_sync();
-    };
-    if constexpr (!BLF_FBD_CSUB) {
-        link_step();
-        FSTAMP_ADD(2, f_t2);
-        FSTAMP(f_t3);
-        contacts_step();
-        FSTAMP_ADD(3, f_t3);
-    } else {
-        FSTAMP(f_t3);
-        contacts_step();
-        FSTAMP_ADD(3, f_t3);
-        FSTAMP(f_t2b);
-        link_step();
-        wave_sync();
-        FSTAMP_ADD(2, f_t2b);
-    }
-    static_assert(!ABA || BLF_FBD_CSUB, "the ABA layout needs the contacts before step 3");
+    FSTAMP_ADD(2, f_t2);
     if constexpr (ABA) {   // steps 5-9 replaced by the articulated-body solve (no regularisation)
         FSTAMP(f_t4a);
         const bool ok = fbd_aba<HW, PRI>(m, S, tau, bp, T, lane);
@@ -1102,27 +924,12 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
     //    = prefix[n - 1] + its own link terms: 5-6 shuffle levels instead of one LDS round trip
     //    and wave sync per tree level.  Other orders: level by level from the leaves up.
     if (T.dfs) {
-        const int src = lane > 0 ? lane - 1 : 0;
         constexpr int G = 4;   // components per group (registers)
 #pragma unroll
         for (int g = 0; g < kComp; g += G) {
-            double v[G], pre[G];
-            double bo[G];   // the base link's own terms (every lane reads them: no branch)
+            double pre[G];
 #pragma unroll
-            for (int q = 0; q < G; ++q) {
-                v[q] = jl ? S.link()[S.lrec * (lane + 1) + kSI + g + q] : 0.0;
-                bo[q] = kPrefixLds ? 0.0 : S.link()[kSI + g + q];
-            }
-            if constexpr (!BLF_FBD_CSUB)
-            for (int c = 0; c < ct.C; ++c) {
-                const double* sc = S.cscr() + kCs * c;
-                if (jl && (int)sc[9] == lane + 1)
-#pragma unroll
-                    for (int q = 0; q < G; ++q)
-                        if (g + q >= 10) v[q] = v[q] - sc[g + q];
-            }
-#pragma unroll
-            for (int q = 0; q < G; ++q) pre[q] = v[q];
+            for (int q = 0; q < G; ++q) pre[q] = jl ? S.link()[S.lrec * (lane + 1) + kSI + g + q] : 0.0;
             // inclusive prefix over the half's lanes by DPP (VALU moves, no LDS round trip): row
             // shifts 1, 2, 4, 8 inside each row of 16, then rows 1 / 3 add lane 15 of rows 0 / 2
             // (for HW = 64 also rows 2, 3 add lane 31) -- the QP kernels' forward tree levels
@@ -1141,41 +948,12 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
             level(std::integral_constant<int, 3>{});
             level(std::integral_constant<int, 4>{});
             if constexpr (HW == 64) level(std::integral_constant<int, 5>{});
-            if constexpr (kPrefixLds) {   // step 6 takes prefix[last_j] - prefix[j - 1] itself
+            // the prefix sums go to LDS as they are: step 6 takes prefix[last_j] - prefix[j - 1]
+            // itself (gathering them here by lane shuffles: 4.077 / 4.074 against 3.812 / 3.811 ms
+            // per c5 period, profiles/r04_fbd_prefix_opq_ab.log)
 #pragma unroll
-                for (int q = 0; q < G; ++q)
-                    if (jl) S.comp()[kCompS * lane + g + q] = pre[q];
-                (void)bo;
-                (void)src;
-                continue;
-            }
-#pragma unroll
-            for (int q = 0; q < G; ++q) {
-#if BLF_FBD_SCANX
-                // the previous lane's prefix by a DPP wavefront rotation (a half's lane 0 does not
-                // use it) and the total by v_readlane: one ds_bpermute per component, not three
-                const double atl = __shfl(pre[q], T.last, HW);
-                const double bef = qp::dpp1<qp::kPrevWrap>(pre[q]);
-                const double tot = H.bcast_k(pre[q], n - 1);
-                (void)src;
-#else
-                const double atl = __shfl(pre[q], T.last, HW);
-                const double bef = __shfl(pre[q], src, HW);
-                const double tot = __shfl(pre[q], n - 1, HW);
-#endif
-                if (jl) S.comp()[kCompS * lane + g + q] = lane > 0 ? atl - bef : atl;
-                if constexpr (BLF_FBD_CSUB) {
-                    const double b = bo[q] + tot;
-                    if (lane == 0) S.comp()[kCompS * n + g + q] = b;
-                } else if (lane == 0) {
-                    double b = bo[q] + tot;
-                    for (int c = 0; c < ct.C; ++c) {
-                        const double* sc = S.cscr() + kCs * c;
-                        if (g + q >= 10 && (int)sc[9] == 0) b = b - sc[g + q];
-                    }
-                    S.comp()[kCompS * n + g + q] = b;
-                }
-            }
+            for (int q = 0; q < G; ++q)
+                if (jl) S.comp()[kCompS * lane + g + q] = pre[q];
         }
         wave_sync();
     } else
@@ -1187,13 +965,6 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
             double acc[kComp];
 #pragma unroll
             for (int p = 0; p < kComp; ++p) acc[p] = S.link()[S.lrec * l + kSI + p];
-            if constexpr (!BLF_FBD_CSUB)
-            for (int c = 0; c < ct.C; ++c) {
-                const double* sc = S.cscr() + kCs * c;
-                if ((int)sc[9] == l)
-#pragma unroll
-                    for (int p = 10; p < kComp; ++p) acc[p] = acc[p] - sc[p];
-            }
             for (unsigned long long b = ch; b; b &= b - 1) {
                 const double* cs = S.comp() + kCompS * __builtin_ctzll(b);
 #pragma unroll
@@ -1229,7 +1000,7 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
             }
         }
         double Iv[kComp];
-        if (kPrefixLds && T.dfs) {   // the subtree sums from the prefix sums step 5 left
+        if (T.dfs) {   // the subtree sums from the prefix sums step 5 left
             const int j = c - 6;
             const double* hp = S.comp() + kCompS * (c < 6 ? n - 1 : T.lastc);
             const double* lp = c < 6 ? S.link() + kSI : S.comp() + kCompS * (j > 0 ? j - 1 : 0);
@@ -1278,26 +1049,17 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
             if (j < NV && j <= lane) r[j] = r[j] + reg[NV * lane + j];
     FSTAMP_ADD(6, f_t6);
     FSTAMP(f_t7);
-    // 8. Cholesky M = L L^T, right-looking, lane i keeps row i in registers, CB columns per step
-    //    (BLF_FBD_CHOLB; 1: one column per step): every lane factors the step's CB x CB diagonal
-    //    block from its broadcast entries (rows past the matrix: identity), computes its own CB
-    //    entries by the same forward substitution (so a lane inside the block reproduces the
-    //    block's row bit for bit), and the CB columns of the rows below go through one LDS buffer
-    //    set (two sets, alternating) and are read back as broadcasts: one LDS round trip per CB
-    //    pivots, where the dependent chain of pivot, column store and read-back is the
-    //    Cholesky's time at one wavefront per SIMD
+    // 8. Cholesky M = L L^T, right-looking, lane i keeps row i in registers, CB columns per step:
+    //    every lane factors the step's CB x CB diagonal block from its broadcast entries (rows past
+    //    the matrix: identity), computes its own CB entries by the same forward substitution (so a
+    //    lane inside the block reproduces the block's row bit for bit), and the CB columns of the
+    //    rows below go through one LDS buffer set (two sets, alternating) and are read back as
+    //    broadcasts: one LDS round trip per CB pivots, where the dependent chain of pivot, column
+    //    store and read-back is the Cholesky's time at one wavefront per SIMD
     bool ok = true;
-#if BLF_FBD_CHOLB > 1
     // the block must divide the register row (NVMAX = 54 for the largest model: 2)
-    constexpr int CB = NVMAX % BLF_FBD_CHOLB == 0 ? BLF_FBD_CHOLB : 2;
+    constexpr int CB = 2;
     static_assert(NVMAX % CB == 0, "block size divides the register row");
-    // FOLD >= 1: the forward substitution L z = y rides along: every lane also solves the block's
-    // CB unknowns z_{k..k+CB-1} from the broadcast y entries of the block's lanes, the block's
-    // lanes keep theirs, the rows below subtract L_{lane,k+i} z_{k+i}: no separate loop of NV
-    // dependent broadcasts.  FOLD == 2: the columns also go to their final place, L column-major
-    // over the dead link records (Lm[MS c + row], odd MS), which the back substitution then reads
-    // lane-strided, instead of a separate row-major store of L.
-    double* Lm = S.link();
 #pragma unroll
     for (int k = 0; k < NVMAX; k += CB) {
         if (k < NV) {
@@ -1320,8 +1082,6 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
                 double q = __builtin_amdgcn_rsq(d);
                 il[i] = q * (1.5 - (0.5 * d) * (q * q));
                 Lb[i][i] = d * il[i];
-                // 1 / L_kk for the substitutions (BLF_FBD_SUBST); S.rhs() is free until the end
-                if (kSubst && HW == 32 && lane == 0 && k + i < NV) S.rhs()[k + i] = il[i];
             }
             // this lane's entries L_{lane,k..k+CB-1} (upper-triangle junk inside the block, unread)
             double li[CB];
@@ -1332,154 +1092,39 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
                 for (int c = 0; c < i; ++c) t = t - li[c] * Lb[i][c];
                 li[i] = t * il[i];
             }
-            if constexpr (FOLD >= 1) {
-            double z[CB];
-#pragma unroll
-            for (int i = 0; i < CB; ++i) {
-                double t = k + i < NV ? H.bcast_k(y, k + i) : 0.0;
-#pragma unroll
-                for (int c = 0; c < i; ++c) t = t - Lb[i][c] * z[c];
-                z[i] = t * il[i];
-            }
-            double yl = y;
-#pragma unroll
-            for (int i = 0; i < CB; ++i) yl = yl - li[i] * z[i];
-#pragma unroll
-            for (int i = 0; i < CB; ++i) y = lane == k + i ? z[i] : y;
-            y = lane >= k + CB ? yl : y;
-            }
-            // BLF_FBD_COLFIX: the column sets at the compile-time stride NVMAX, every lane of the
-            // rows (padding lanes: zeros) writing its entry, so the update reads every row at a
-            // constant offset (no clamped per-row address registers; paired LDS reads)
-            constexpr int kColS = BLF_FBD_COLFIX ? NVMAX : 0;
-            double* col = FOLD >= 2 ? Lm + MS * k
-                                    : S.comp() + ((k / CB) & 1) * CB * (BLF_FBD_COLFIX ? NVMAX : NV);
-            const int cst = FOLD >= 2 ? MS : (BLF_FBD_COLFIX ? kColS : NV);
-#define FBD_COL(i, row) col[(i) * cst + (row)]
+            // the step's column set: CB columns at stride NV (a compile-time stride of NVMAX made
+            // the Cholesky itself faster, 19.9k -> 14.8k cycles in fbd_dynamics_kernel, but one c5
+            // period of the Euler kernel slower, 4.04 / 4.02 against 3.77 / 3.76 ms;
+            // profiles/r04_fbd_colfix_cstage_ab.log)
+            double* col = S.comp() + ((k / CB) & 1) * CB * NV;
 #pragma unroll
             for (int i = 0; i < CB; ++i) {
                 r[k + i] = lane >= k ? li[i] : r[k + i];
-                if ((BLF_FBD_COLFIX && FOLD < 2 ? lane < NVMAX : lane < NV) && k + i < NV) FBD_COL(i, lane) = r[k + i];
+                if (lane < NV && k + i < NV) col[i * NV + lane] = r[k + i];
             }
-            wave_sync();
-            // no row predicate (as below): lanes above row j update only upper-triangle entries
-#pragma unroll
-            for (int j = k + CB; j < NVMAX; ++j) {
-                const int jj = (BLF_FBD_COLFIX && FOLD < 2) ? j : (j < NV ? j : NV - 1);
-                double t = r[j];
-#pragma unroll
-                for (int i = CB - 1; i >= 0; --i) t = fma(-r[k + i], FBD_COL(i, jj), t);
-                r[j] = t;
-            }
-#undef FBD_COL
-        }
-    }
-#else
-    // 8. Cholesky M = L L^T, right-looking, lane i keeps row i in registers; column k of the
-    //    rows below the pivot goes through an LDS buffer (two, alternating) and is read back as
-    //    broadcasts
-#pragma unroll
-    for (int k = 0; k < NVMAX; ++k) {
-        if (k < NV) {
-            const double piv = H.bcast_k(r[k], k);
-            ok = ok && (piv > 0.0);
-            // 1 / sqrt(piv): v_rsq_f64 and one Newton step (the factorization's accuracy is that
-            // of its rounding errors; parity with the oracle is at 1e-9)
-            double isq = __builtin_amdgcn_rsq(piv);
-            isq = isq * (1.5 - (0.5 * piv) * (isq * isq));
-            r[k] = lane == k ? piv * isq : (lane > k ? r[k] * isq : r[k]);
-            double* col = S.comp() + (k & 1) * NV;
-            if (lane < NV) col[lane] = r[k];
             wave_sync();
             // No row predicate: a lane above row j only updates its upper-triangle entry r[j],
             // which nothing reads (pivots are diagonal, the substitutions and the stored L use
-            // j <= lane), so the update is one LDS broadcast read and one fma per entry.  j >= NV
-            // touches only lanes past the matrix.
+            // j <= lane), so the update is CB LDS broadcast reads and fmas per entry (parity with
+            // the oracle is 1e-9 relative, not bitwise).  j >= NV touches only lanes past the matrix.
 #pragma unroll
-            for (int j = k + 1; j < NVMAX; ++j) {
-                const double ljk = col[j < NV ? j : NV - 1];
-                r[j] = fma(-r[k], ljk, r[j]);   // parity here is 1e-9 relative, not bitwise
+            for (int j = k + CB; j < NVMAX; ++j) {
+                const int jj = j < NV ? j : NV - 1;
+                double t = r[j];
+#pragma unroll
+                for (int i = CB - 1; i >= 0; --i) t = fma(-r[k + i], col[i * NV + jj], t);
+                r[j] = t;
             }
         }
     }
-#endif
     FSTAMP_ADD(7, f_t7);
     FSTAMP(f_t8);
-#if BLF_FBD_CHOLB > 1
-    if constexpr (FOLD == 1) {
-    // 9. L z = y is done (folded into the factorization); L^T x = z with row k of L read from
-    //    LDS (the link records are dead by now), one step ahead
-    const double idg = lane < NV ? 1.0 / bcast_own_diag<NVMAX>(r, lane) : 0.0;
-    if (lane < NV)
-#pragma unroll
-        for (int j = 0; j < NVMAX; ++j)
-            if (j < NV && j <= lane) Lm[MS * lane + j] = r[j];
-    wave_sync();
-    double lki = (lane < NV - 1) ? Lm[MS * (NV - 1) + lane] : 0.0;
-    for (int k = NV - 1; k >= 0; --k) {
-        const double lnext = (k > 0 && lane < k - 1) ? Lm[MS * (k - 1) + lane] : 0.0;   // read ahead
-        if (lane == k) y = y * idg;
-        const double xk = H.bcast_k(y, k);
-        if (lane < k) y = y - lki * xk;
-        lki = lnext;
-    }
-    } else if constexpr (FOLD >= 2) {
-    // 9. L z = y is done (folded into the factorization); L^T x = z with L's row k read from the
-    //    column-major L (Lm[MS lane + k] = L_{k,lane}, lane-strided, one step ahead); lane k
-    //    scales its own entry, one broadcast per step
-    const double idg = lane < NV ? 1.0 / bcast_own_diag<NVMAX>(r, lane) : 0.0;
-    double lki = (lane < NV - 1) ? Lm[MS * lane + (NV - 1)] : 0.0;
-    for (int k = NV - 1; k >= 0; --k) {
-        const double lnext = (k > 0 && lane < k - 1) ? Lm[MS * lane + (k - 1)] : 0.0;   // read ahead
-        if (lane == k) y = y * idg;
-        const double xk = H.bcast_k(y, k);
-        if (lane < k) y = y - lki * xk;
-        lki = lnext;
-    }
-    } else {
-#endif
     // 9. L z = y with the rows in registers, then L^T x = z with row k of L read from LDS (the
     //    link records are dead by now); lane k scales its own entry, one broadcast per step.  Two
     //    unknowns per step (the 2 x 2 block solved by every lane, as in the factorization) measured
-    //    the same: 6.054 / 6.069 against 6.081 / 6.073 ms per c5 period of the Euler kernel
-    if constexpr (kSubst && HW == 32) {
-    // BLF_FBD_SUBST (two systems per wavefront; LLVM's register allocator crashes on it in the
-    // one-system instantiations): the unknown's scaling rides on the multiplier, not on the broadcast value:
-    // step k broadcasts lane k's unscaled entry t_k and the rows update y_i -= (L_ik / L_kk) t_k,
-    // whose factor is known ahead; the pivots 1 / L_kk come from the factorization (S.rhs()), and
-    // every entry is scaled once at the end.  Per step the dependent chain is the broadcast and
-    // one fma (was: scale, select, broadcast, multiply, subtract).
-    const double* ilv = S.rhs();
-    const double idg = lane < NV ? ilv[lane] : 0.0;
-    double ilk = ilv[0];
-#pragma unroll
-    for (int k = 0; k < NVMAX; ++k) {   // k >= NV changes only lanes past the matrix
-        const double ilnext = ilv[k + 1 < NV ? k + 1 : NV - 1];   // read ahead
-        const double t = H.bcast_k(y, k);
-        const double f = lane > k ? r[k] * ilk : 0.0;
-        y = fma(-f, t, y);
-        ilk = ilnext;
-    }
-    y = y * idg;
-    double* Lr = S.link();
-    if (lane < NV)
-#pragma unroll
-        for (int j = 0; j < NVMAX; ++j)
-            if (j < NV && j <= lane) Lr[MS * lane + j] = r[j];
-    wave_sync();
-    double lki = (lane < NV - 1) ? Lr[MS * (NV - 1) + lane] : 0.0;
-    ilk = ilv[NV - 1];
-    for (int k = NV - 1; k >= 0; --k) {
-        const double lnext = (k > 0 && lane < k - 1) ? Lr[MS * (k - 1) + lane] : 0.0;   // read ahead
-        const double ilnext = ilv[k > 0 ? k - 1 : 0];
-        const double t = H.bcast_k(y, k);
-        const double f = lane < k ? lki * ilk : 0.0;
-        y = fma(-f, t, y);
-        lki = lnext;
-        ilk = ilnext;
-    }
-    y = y * idg;
-    } else {
+    //    the same: 6.054 / 6.069 against 6.081 / 6.073 ms per c5 period of the Euler kernel; the
+    //    pivot scaling on the multipliers instead of the unknowns was slower, 3.914 / 3.904 against
+    //    3.792 / 3.792 ms (profiles/r04_fbd_subst_ab.log)
     const double idg = lane < NV ? 1.0 / bcast_own_diag<NVMAX>(r, lane) : 0.0;
 #pragma unroll
     for (int k = 0; k < NVMAX; ++k) {   // k >= NV changes only lanes past the matrix
@@ -1502,10 +1147,6 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
         if (lane < k) y = y - lki * xk;
         lki = lnext;
     }
-    }
-#if BLF_FBD_CHOLB > 1
-    }
-#endif
     if (lane < NV) S.rhs()[lane] = y;
     wave_sync();
     FSTAMP_ADD(8, f_t8);
@@ -1541,8 +1182,8 @@ __global__ __launch_bounds__(64) void fbd_dynamics_kernel(Model m, blf_fb_state 
     }
     wave_sync();
     const Topo T = build_topo<HW>(m, S);
-    const bool ok = fbd_eval<NVMAX, HW, PRI, 0, false, false, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
-                                        tau + (int64_t)n * q, ct, q, reg, T);
+    const bool ok = fbd_eval<NVMAX, HW, PRI, false, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
+                                                         tau + (int64_t)n * q, ct, q, reg, T);
     if (!active) return;
     const double nan = __builtin_nan("");
     for (int c = lane; c < NV; c += HW) {
@@ -1578,44 +1219,11 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const Half<HW> H;
     const int n = m.n, NV = n + 6;
-    // BLF_FBD_LDSMODEL (two systems per wavefront): the model's per-joint / per-link constants,
-    // the gains and the contacts' frames copied once into a block at the start of LDS, at
-    // compile-time offsets, so the Euler loop reads them from LDS and holds no pointers to them
-    constexpr bool kLM = BLF_FBD_LDSMODEL && HW == 32;
-    constexpr bool kCS = BLF_FBD_CSTAGE && !kLM && HW == 32;   // (LLVM's allocator crashes on the HW = 64 form)
-    constexpr int kMB = kLM ? fbd_model_block<NVMAX>() : 0;
-    const Smem S(smem + kMB + H.half * Smem(nullptr, n, ct.C, ABA).total, n, ct.C, ABA);
+    // the per-system constants of the Euler loop staged in LDS: the two-systems form only (LLVM's
+    // allocator crashes on the HW = 64 form)
+    constexpr bool kCS = HW == 32;
+    const Smem S(smem + H.half * Smem(nullptr, n, ct.C, ABA).total, n, ct.C, ABA);
     const int lane = H.hl;
-    if constexpr (kLM) {
-        constexpr int J = NVMAX - 6, Lk = NVMAX - 5;
-        constexpr int oA = 0, oR = oA + 3 * J, oC = oR + 9 * J, oI = oC + 3 * Lk, oM = oI + 9 * Lk;
-        constexpr int oKp = oM + Lk, oKd = oKp + J, oP = oKd + J, oL = oP + 12 * BLF_FBD_MAX_CONTACTS;
-        const int t = threadIdx.x, L = n + 1;
-        for (int i = t; i < 3 * n; i += kWave) smem[oA + i] = m.jaxis[i];
-        for (int i = t; i < 9 * n; i += kWave) smem[oR + i] = m.jrot[i];
-        for (int i = t; i < 3 * L; i += kWave) smem[oC + i] = m.com[i];
-        for (int i = t; i < 9 * L; i += kWave) smem[oI + i] = m.inertia[i];
-        for (int i = t; i < L; i += kWave) smem[oM + i] = m.mass[i];
-        if (imp.kp)
-            for (int i = t; i < n; i += kWave) {
-                smem[oKp + i] = imp.kp[i];
-                smem[oKd + i] = imp.kd[i];
-            }
-        for (int i = t; i < 12 * ct.C; i += kWave) smem[oP + i] = m.fpose[12 * ct.frame[i / 12] + i % 12];
-        for (int i = t; i < ct.C; i += kWave) smem[oL + i] = (double)m.flink[ct.frame[i]];
-        wave_sync();
-        m.jaxis = smem + oA;
-        m.jrot = smem + oR;
-        m.com = smem + oC;
-        m.inertia = smem + oI;
-        m.mass = smem + oM;
-        m.cpose = smem + oP;
-        m.clink = smem + oL;
-        if (imp.kp) {
-            imp.kp = smem + oKp;
-            imp.kd = smem + oKd;
-        }
-    }
     constexpr int per = kWave / HW;   // systems per wavefront
     const Topo T = build_topo<HW>(m, S);
     double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n | dR 9
@@ -1634,7 +1242,7 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m
         else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
         loc[i] = v;
     }
-    if constexpr (kCS) {   // this system's constants of the Euler loop, once (BLF_FBD_CSTAGE)
+    if constexpr (kCS) {   // this system's constants of the Euler loop, once (Smem o_cst / o_imp)
         const int C = ct.C;
         for (int i = lane; i < 29 * C; i += HW) {
             double v;
@@ -1666,8 +1274,8 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m
             wave_sync();
             tq = S.tq();
         }
-        ok = fbd_eval<NVMAX, HW, PRI, BLF_FBD_FOLD, kLM, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
-                                 tq, ct, q, reg, T) && ok;
+        ok = fbd_eval<NVMAX, HW, PRI, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
+                                                tq, ct, q, reg, T) && ok;
         if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, loc + 3, dR);
         wave_sync();
         // every element moves by its derivative at the start of the step (ForwardEuler.tpp:37-45):
@@ -1896,7 +1504,6 @@ blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, cons
                             const blf_joint_impedance* impedance)
 {
     if (batch == 0) return BLF_OK;
-    const size_t mb32 = BLF_FBD_LDSMODEL ? sizeof(double) * fbd_model_block<32>() : 0;
     const Contacts c = to_contacts(ct);
     Impedance imp{nullptr, nullptr, nullptr};
     if (impedance) imp = Impedance{impedance->kp, impedance->kd, impedance->q_ref};
@@ -1905,7 +1512,7 @@ blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, cons
 #define FBD_EUL(NV, HW) (pri ? (aba ? fbd_euler_kernel<NV, HW, true, true> : fbd_euler_kernel<NV, HW, true, false>) \
                              : (aba ? fbd_euler_kernel<NV, HW, false, true> : fbd_euler_kernel<NV, HW, false, false>))
     if (md->ndof + 6 <= 32)   // two systems per wavefront
-        hipLaunchKernelGGL(FBD_EUL(32, 32), dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds + mb32, s,
+        hipLaunchKernelGGL(FBD_EUL(32, 32), dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds, s,
                            to_model(md), *st, tau, c, reg, nsteps, dT, dT_last, imp, batch);
     else
         hipLaunchKernelGGL(FBD_EUL(BLF_FBD_MAX_DOFS + 6, kWave), dim3((unsigned)batch), dim3(kWave), lds, s,
