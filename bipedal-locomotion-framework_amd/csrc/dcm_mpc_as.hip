@@ -87,6 +87,19 @@ struct AKnotT {
 };
 using AKnot = AKnotT<double>;
 
+// A slot of the fp64 passes before its knot's loads (and for good where the lane holds no knot,
+// k >= N): all zero but al, which every caller sets after the loads (1 + be).
+template <class T>
+__device__ __forceinline__ void knot_zero(AKnotT<T>& K)
+{
+    K.m = 0;
+    K.gm = K.drop = K.add = 0;
+    K.r0 = K.r1 = K.x0 = K.x1 = K.w = K.be = T(0);
+    K.rh0 = K.rh1 = K.d0 = K.d1 = K.qx0 = K.qx1 = T(0);
+    K.P00 = K.P01 = K.P11 = K.h00 = K.h01 = K.h11 = T(0);
+    K.rr0 = K.rr1 = K.xr0 = K.xr1 = T(0);
+}
+
 // The QP's facet rows in LDS, [M][S] normals and [M][S] offsets (facet i of column col at
 // i S + col), fp64 (rounded to float as the fp32 search reads them).
 template <class V, int MF = kMaxFacets>
@@ -114,24 +127,8 @@ struct LdsRows<float, MF> {
     __device__ int at(int i, int col) const { return (int)__umul24((unsigned)i, (unsigned)S) + col; }
 };
 
-// BLF_AS_MINWAVES: the fused cold kernel's __launch_bounds__ waves per SIMD (A/B builds);
-#ifndef BLF_AS_MINWAVES
-#define BLF_AS_MINWAVES 2
-#endif
-#ifndef BLF_AS_OVERLAP
-#define BLF_AS_OVERLAP 1
-#endif
-#ifndef BLF_AS_KEEPIN
-#define BLF_AS_KEEPIN 1
-#endif
-// A/B builds only (the oracle restates the product, 1 / 1): the anti-cycling rule of the fp64
-// passes and the refinement of multiplier-1e4+ optima
-#ifndef BLF_AS_ANTICYCLE
-#define BLF_AS_ANTICYCLE 1
-#endif
-#ifndef BLF_AS_REFINE
-#define BLF_AS_REFINE 1
-#endif
+// waves per SIMD the active-set kernels' register allocation must allow (__launch_bounds__)
+constexpr int kAsMinWaves = 2;
 
 // One facet row (normal, offset) in the scalar type of the pass.
 template <class T>
@@ -229,6 +226,24 @@ __device__ __forceinline__ void rc_tree(RcT<T>& e, bool& ok, int lane)
     if (tree_has<L, false>(lane)) ok = rc_combine(e, q) && ok;
 }
 
+// The Kogge-Stone levels of the kTreeKS / kTreePad trees: at distance d the partner of lane l is
+// lane l - d (FWD) or l + d; distance 1 moves by DPP, 2..32 by ds_bpermute.
+//   ks_addr: the partner's ds_bpermute address.  kTreeKS wraps the index; kTreePad (PAD) sends a
+//            lane whose partner lies outside the wavefront to lane 63's zero element / identity;
+//   ks_has:  whether the lane combines: every lane in kTreePad, else those with a partner inside.
+template <bool PAD, bool FWD>
+__device__ __forceinline__ int ks_addr(int ln, int d)
+{
+    if constexpr (FWD) return (PAD ? (ln >= d ? ln - d : kWave - 1) : ((ln - d) & (kWave - 1))) << 2;
+    else return (PAD ? min(ln + d, kWave - 1) : ((ln + d) & (kWave - 1))) << 2;
+}
+
+template <bool PAD, bool FWD>
+__device__ __forceinline__ bool ks_has(int ln, int d)
+{
+    return PAD || (FWD ? ln >= d : ln + d < kWave);
+}
+
 // Backward affine scan v_k = G_k v_{k+1} + c_k, v_N = 0.  Returns v_{k+1} per slot.
 template <int KPL, int TR, class T>
 __device__ __forceinline__ void as_scan_backward(const T (&G)[KPL][4], const T (&c)[KPL][2], int lane,
@@ -240,31 +255,20 @@ __device__ __forceinline__ void as_scan_backward(const T (&G)[KPL][4], const T (
     const int ln = opaque(lane);
     if constexpr (TR == kTreeDpp) {
         aff_tree<false>(g0, g1, g2, g3, e0, e1, lane);
-    } else if (KPL == 2 && TR == kTreePad) {
-        {   // d = 1 (DPP)
-            const T p0 = dpp1<kNextKeep>(g0), p1 = dpp1<kNextKeep>(g1), p2 = dpp1<kNextKeep>(g2);
-            const T p3 = dpp1<kNextKeep>(g3), q0 = dpp1<kNextKeep>(e0), q1 = dpp1<kNextKeep>(e1);
-            COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
-        }
-#pragma unroll
-        for (int d = 2; d < kWave; d <<= 1) {
-            const int ad = min(ln + d, kWave - 1) << 2;
-            const T p0 = bperm(ad, g0), p1 = bperm(ad, g1), p2 = bperm(ad, g2), p3 = bperm(ad, g3);
-            const T q0 = bperm(ad, e0), q1 = bperm(ad, e1);
-            COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
-        }
     } else {
-        {
-            const T p0 = dpp1<kNextWrap>(g0), p1 = dpp1<kNextWrap>(g1), p2 = dpp1<kNextWrap>(g2);
-            const T p3 = dpp1<kNextWrap>(g3), q0 = dpp1<kNextWrap>(e0), q1 = dpp1<kNextWrap>(e1);
-            if (ln + 1 < kWave) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
+        constexpr bool pad = KPL == 2 && TR == kTreePad;
+        {   // d = 1 (DPP; as_pad: lane 63 keeps its own zero element)
+            constexpr int C = pad ? kNextKeep : kNextWrap;
+            const T p0 = dpp1<C>(g0), p1 = dpp1<C>(g1), p2 = dpp1<C>(g2);
+            const T p3 = dpp1<C>(g3), q0 = dpp1<C>(e0), q1 = dpp1<C>(e1);
+            if (ks_has<pad, false>(ln, 1)) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
         }
 #pragma unroll
         for (int d = 2; d < kWave; d <<= 1) {
-            const int ad = ((ln + d) & (kWave - 1)) << 2;
+            const int ad = ks_addr<pad, false>(ln, d);
             const T p0 = bperm(ad, g0), p1 = bperm(ad, g1), p2 = bperm(ad, g2), p3 = bperm(ad, g3);
             const T q0 = bperm(ad, e0), q1 = bperm(ad, e1);
-            if (ln + d < kWave) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
+            if (ks_has<pad, false>(ln, d)) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
         }
     }
     // e = v at this lane's first knot; the next lane's = v past this lane's last knot
@@ -296,31 +300,19 @@ __device__ __forceinline__ void as_scan_forward(const T (&F)[KPL][4], const T (&
     const int ln = opaque(lane);
     if constexpr (TR == kTreeDpp) {
         aff_tree<true>(g0, g1, g2, g3, e0, e1, lane);
-    } else if (KPL == 2 && TR == kTreePad) {   // lanes before the first partner take lane 63's zero element (as_pad)
-        {   // d = 1 (DPP; lane 0 takes lane 63's)
-            const T p0 = dpp1<kPrevWrap>(g0), p1 = dpp1<kPrevWrap>(g1), p2 = dpp1<kPrevWrap>(g2);
-            const T p3 = dpp1<kPrevWrap>(g3), q0 = dpp1<kPrevWrap>(e0), q1 = dpp1<kPrevWrap>(e1);
-            COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
-        }
-#pragma unroll
-        for (int d = 2; d < kWave; d <<= 1) {
-            const int ad = (ln >= d ? ln - d : kWave - 1) << 2;
-            const T p0 = bperm(ad, g0), p1 = bperm(ad, g1), p2 = bperm(ad, g2), p3 = bperm(ad, g3);
-            const T q0 = bperm(ad, e0), q1 = bperm(ad, e1);
-            COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
-        }
     } else {
-        {
+        constexpr bool pad = KPL == 2 && TR == kTreePad;
+        {   // d = 1 (DPP; as_pad: lane 0 takes lane 63's zero element)
             const T p0 = dpp1<kPrevWrap>(g0), p1 = dpp1<kPrevWrap>(g1), p2 = dpp1<kPrevWrap>(g2);
             const T p3 = dpp1<kPrevWrap>(g3), q0 = dpp1<kPrevWrap>(e0), q1 = dpp1<kPrevWrap>(e1);
-            if (ln >= 1) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
+            if (ks_has<pad, true>(ln, 1)) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
         }
 #pragma unroll
         for (int d = 2; d < kWave; d <<= 1) {
-            const int ad = ((ln - d) & (kWave - 1)) << 2;
+            const int ad = ks_addr<pad, true>(ln, d);
             const T p0 = bperm(ad, g0), p1 = bperm(ad, g1), p2 = bperm(ad, g2), p3 = bperm(ad, g3);
             const T q0 = bperm(ad, e0), q1 = bperm(ad, e1);
-            if (ln >= d) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
+            if (ks_has<pad, true>(ln, d)) COMPOSE(g0, g1, g2, g3, p0, p1, p2, p3, q0, q1, e0, e1);
         }
     }
     // e = x past this lane's last knot; the previous lane's = x at this lane's first knot
@@ -413,17 +405,10 @@ __device__ __forceinline__ bool as_riccati(AKnotT<T> (&K)[KPL], const PT<T>& P, 
         q.h0 = bperm(ad, e.h0); q.h1 = bperm(ad, e.h1); q.h2 = bperm(ad, e.h2);
     };
     auto level1 = [&](RcT<T>& q) {   // d = 1 (DPP; as_pad: lane 63 keeps its own identity)
-        if (pad) {
-            q.a0 = dpp1<kNextKeep>(e.a0); q.a1 = dpp1<kNextKeep>(e.a1);
-            q.a2 = dpp1<kNextKeep>(e.a2); q.a3 = dpp1<kNextKeep>(e.a3);
-            q.g0 = dpp1<kNextKeep>(e.g0); q.g1 = dpp1<kNextKeep>(e.g1); q.g2 = dpp1<kNextKeep>(e.g2);
-            q.h0 = dpp1<kNextKeep>(e.h0); q.h1 = dpp1<kNextKeep>(e.h1); q.h2 = dpp1<kNextKeep>(e.h2);
-        } else {
-            q.a0 = dpp1<kNextWrap>(e.a0); q.a1 = dpp1<kNextWrap>(e.a1);
-            q.a2 = dpp1<kNextWrap>(e.a2); q.a3 = dpp1<kNextWrap>(e.a3);
-            q.g0 = dpp1<kNextWrap>(e.g0); q.g1 = dpp1<kNextWrap>(e.g1); q.g2 = dpp1<kNextWrap>(e.g2);
-            q.h0 = dpp1<kNextWrap>(e.h0); q.h1 = dpp1<kNextWrap>(e.h1); q.h2 = dpp1<kNextWrap>(e.h2);
-        }
+        constexpr int C = pad ? kNextKeep : kNextWrap;
+        q.a0 = dpp1<C>(e.a0); q.a1 = dpp1<C>(e.a1); q.a2 = dpp1<C>(e.a2); q.a3 = dpp1<C>(e.a3);
+        q.g0 = dpp1<C>(e.g0); q.g1 = dpp1<C>(e.g1); q.g2 = dpp1<C>(e.g2);
+        q.h0 = dpp1<C>(e.h0); q.h1 = dpp1<C>(e.h1); q.h2 = dpp1<C>(e.h2);
     };
     if constexpr (TR == kTreeDpp) {
         rc_tree<0>(e, ok, lane);
@@ -432,29 +417,17 @@ __device__ __forceinline__ bool as_riccati(AKnotT<T> (&K)[KPL], const PT<T>& P, 
         rc_tree<3>(e, ok, lane);
         rc_tree<4>(e, ok, lane);
         rc_tree<5>(e, ok, lane);
-    } else if (pad) {   // past the wavefront: lane 63's identity (as_pad)
-        {
-            RcT<T> q;
-            level1(q);
-            ok = rc_combine(e, q) && ok;
-        }
-#pragma unroll
-        for (int d = 2; d < kWave; d <<= 1) {
-            RcT<T> q;
-            level(min(ln + d, kWave - 1) << 2, q);
-            ok = rc_combine(e, q) && ok;
-        }
     } else {
         {
             RcT<T> q;
             level1(q);
-            if (ln + 1 < kWave) ok = rc_combine(e, q) && ok;
+            if (ks_has<pad, false>(ln, 1)) ok = rc_combine(e, q) && ok;
         }
 #pragma unroll
         for (int d = 2; d < kWave; d <<= 1) {
             RcT<T> q;
-            level(((ln + d) & (kWave - 1)) << 2, q);
-            if (ln + d < kWave) ok = rc_combine(e, q) && ok;
+            level(ks_addr<pad, false>(ln, d), q);
+            if (ks_has<pad, false>(ln, d)) ok = rc_combine(e, q) && ok;
         }
     }
     // P at this lane's first knot; the next lane's (terminal past the last lane)
@@ -922,10 +895,6 @@ __device__ __forceinline__ int as_cand(const AKnotT<T>& K)
 // `handover` knots ends the search, its next candidate sets going to the fp64 passes instead of
 // another float pass (oracle passes32): the last float pass before the
 // certifying one changes a few knots, and the fp64 passes certify that set.  -1: never.
-#ifndef BLF_AS_OPQLANE   // A/B: 1 (VGPRs 228 -> 221, SGPR spills 36 -> 44) took 0.127 / 0.128 against 0.125 /
-#define BLF_AS_OPQLANE 0   // 0.126 ms at B = 4096 (profiles/r04_cstage_asopq_ab.log), so 0
-#endif
-
 template <int KPL, int TR, class T, class RS>
 __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, const RS& R, int NH, int N,
                                           int lane, T xi00, T xi01, int (&pk)[KPL],
@@ -934,18 +903,13 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
     T xk[KPL][2];
     as_xi_prev<KPL, T>(K, lane, xi00, xi01, xk);
     bool certified = false;
-    const int lane0 = lane;
     // the fp64 passes: up to kAsPasses, the last ones under the anti-cycling rule (oracle
     // dcm_polish anti_cycle: Bland's rule from pass kGuessPasses on); the fp32 search: kGuessPasses
-    constexpr bool kAnti = sizeof(T) == 8 && BLF_AS_ANTICYCLE;
+    constexpr bool kAnti = sizeof(T) == 8;
     constexpr int kMaxPass = kAnti ? kAsPasses : kGuessPasses;
     int pass = 0;
     for (; pass < kMaxPass; ++pass) {
         const bool bland = kAnti && pass >= kGuessPasses;   // Bland's rule from pass 8 on
-        // BLF_AS_OPQLANE: the lane index opaque per pass, so its masks are recomputed inside the
-        // pass instead of hoisted out of the loop into SGPRs (which spill)
-        int lane = lane0;
-        if constexpr (BLF_AS_OPQLANE) asm volatile("" : "+v"(lane));
         AS_COUNT(count_slot);
         AS_STAMP(t_s);
         T sv[KPL][4];
@@ -1059,8 +1023,8 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
         bool big = false;
 #pragma unroll
         for (int j = 0; j < KPL; ++j) big = big || pl[j][0] > kRefineLam || pl[j][1] > kRefineLam;
-        if (BLF_AS_REFINE && certified && __ballot(big) != 0)
-            as_refine<KPL, TR>(K, P, R, N, lane0, xi00, xi01, pk);
+        if (certified && __ballot(big) != 0)
+            as_refine<KPL, TR>(K, P, R, N, lane, xi00, xi01, pk);
     }
     return certified;
 }
@@ -1349,26 +1313,23 @@ __device__ __forceinline__ void cold_solve(
     // (The phase-indexed input keeps its gathers before the LQ step: issued after the knot loads
     // and committed after the step like the slab loads, it measured 1 % slower on the c3 pipeline,
     // 1.900 / 1.893 against 1.882 / 1.874 ms per step, profiles/r03_ph_overlap_ab.log.)
-    constexpr bool kOverlap = !PH && BLF_AS_OVERLAP && !kWide;
+    constexpr bool kOverlap = !PH && !kWide;
     double2 va[U];
     double vb[U];
     if (PH) {
         ph_stage_phases(ps, p, N, P.dt, lane, sBE, sPh);
         stage_rows_ph<KPL, U, kWide>(ps, sPh, p, N, M, S, NH, lane, A2d, Bv);
-    } else if (kOverlap) {
-        // issued below, after the knot loads: a wait for those (vmcnt counts in issue order) then
-        // leaves the younger row loads in flight
     } else if (kWide) {
         stage_rows_rounds<KPL, U>(Ain, bin, p, N, M, S, NH, lane, A2d, Bv);
-    } else {
-        stage_rows<KPL, U, double>(Ain, bin, p, N, M, S, NH, lane, 0, nA, A2d, Bv);
     }
+    // kOverlap: issued below, after the knot loads: a wait for those (vmcnt counts in issue order)
+    // then leaves the younger row loads in flight
     const LdsRows<double, MF> R{reinterpret_cast<const typename LdsRows<double, MF>::V2*>(smem),
                                 smem + 2 * (size_t)M * S, S, NH};
 
     AKnotT<float> F[KPL];
-    // BLF_AS_KEEPIN: the knots' fp64 inputs kept from phase A's loads for phase B (instead of
-    // reading them from global memory again after the float search)
+    // the knots' fp64 inputs, kept from phase A's loads for phase B (instead of reading them from
+    // global memory again after the float search)
     KnotIn kin[KPL];
     int cand[KPL];         // the float search's next candidate sets (phase B's guess when uncertified)
     bool cert32 = false;   // the float search certified its point
@@ -1379,7 +1340,7 @@ __device__ __forceinline__ void cold_solve(
     for (int j = 0; j < KPL; ++j) {
         const int k = KPL * lane + j;
         AKnotT<float>& Fj = F[j];
-        Fj.m = 0;
+        Fj.m = 0;   // (not knot_zero: r, x and al are set from the references below)
         Fj.gm = Fj.drop = Fj.add = 0;
         Fj.w = Fj.be = 0.0f;
         Fj.rr0 = Fj.rr1 = Fj.xr0 = Fj.xr1 = 0.0f;
@@ -1388,7 +1349,7 @@ __device__ __forceinline__ void cold_solve(
         kin[j] = KnotIn{0, 0.0, 0.0, 0.0, 0.0, 0.0};
         if (k < N) {
             const KnotIn in = knot_in<PH>(p, k, N, omega, xi_ref, vrp_ref, nfacets, ps, sPh);
-            if (BLF_AS_KEEPIN) kin[j] = in;
+            kin[j] = in;
             Fj.m = in.m < 0 ? 0 : in.m > M ? M : in.m;
             Fj.w = float(in.w);
             Fj.be = Pf.dt * Fj.w;
@@ -1433,14 +1394,9 @@ __device__ __forceinline__ void cold_solve(
     for (int j = 0; j < KPL; ++j) {
         const int k = KPL * lane + j;
         AKnot& Kj = K[j];
-        Kj.m = 0;
-        Kj.gm = Kj.drop = Kj.add = 0;
-        Kj.r0 = Kj.r1 = Kj.x0 = Kj.x1 = Kj.w = Kj.be = 0.0;
-        Kj.rh0 = Kj.rh1 = Kj.d0 = Kj.d1 = Kj.qx0 = Kj.qx1 = 0.0;
-        Kj.P00 = Kj.P01 = Kj.P11 = Kj.h00 = Kj.h01 = Kj.h11 = 0.0;
-        Kj.rr0 = Kj.rr1 = Kj.xr0 = Kj.xr1 = 0.0;
+        knot_zero(Kj);
         if (k < N) {
-            const KnotIn in = BLF_AS_KEEPIN ? kin[j] : knot_in<PH>(p, k, N, omega, xi_ref, vrp_ref, nfacets, ps, sPh);
+            const KnotIn in = kin[j];
             Kj.m = in.m;
             Kj.w = in.w;
             Kj.rr0 = in.rr0;
@@ -1522,7 +1478,7 @@ __device__ __forceinline__ void cold_solve(
 }
 
 template <int KPL, bool LAMOUT, bool PH, int TR, int MF>
-__global__ __launch_bounds__(kWave, BLF_AS_MINWAVES) void dcm_mpc_cold_kernel(
+__global__ __launch_bounds__(kWave, kAsMinWaves) void dcm_mpc_cold_kernel(
     KParams P, const double* __restrict__ xi_init, const double* __restrict__ omega,
     const double* __restrict__ xi_ref, const double* __restrict__ vrp_ref,
     const double* __restrict__ Ain, const double* __restrict__ bin,
@@ -1540,7 +1496,7 @@ __global__ __launch_bounds__(kWave, BLF_AS_MINWAVES) void dcm_mpc_cold_kernel(
 // solve is one launch instead of two (the second one's dispatch was 4 us of a 28 us solve, and
 // the host's second enqueue).  Same code, same inputs, so the same bits as the two launches.
 template <bool LAMOUT>
-__global__ __launch_bounds__(kWave, BLF_AS_MINWAVES) void dcm_mpc_cold_fused_kernel(
+__global__ __launch_bounds__(kWave, kAsMinWaves) void dcm_mpc_cold_fused_kernel(
     KParams P, const double* __restrict__ xi_init, const double* __restrict__ omega,
     const double* __restrict__ xi_ref, const double* __restrict__ vrp_ref,
     const double* __restrict__ Ain, const double* __restrict__ bin,
@@ -1559,15 +1515,12 @@ __global__ __launch_bounds__(kWave, BLF_AS_MINWAVES) void dcm_mpc_cold_fused_ker
                                     lam_out);
 }
 
-#ifndef BLF_WARM_RETRY
-#define BLF_WARM_RETRY 1
-#endif
 // ---- the warm-start kernel ("Warm start") ----
 // One wavefront per QP, fp64 facet rows in LDS.  From the shifted previous solution (xi rolled
 // out from its VRPs), guess = the facets the rollout violates plus those whose previous multiplier
 // exceeds the floor, then the fp64 passes (1.7 per window on average: no float search first).
 template <int KPL, bool LAMOUT, bool PH, int TR, int MF>
-__global__ __launch_bounds__(kWave, 2) void dcm_mpc_warm_kernel(
+__global__ __launch_bounds__(kWave, kAsMinWaves) void dcm_mpc_warm_kernel(
     KParams P, const double* __restrict__ xi_init, const double* __restrict__ omega,
     const double* __restrict__ xi_ref, const double* __restrict__ vrp_ref,
     const double* __restrict__ Ain, const double* __restrict__ bin,
@@ -1623,12 +1576,7 @@ __global__ __launch_bounds__(kWave, 2) void dcm_mpc_warm_kernel(
     for (int j = 0; j < KPL; ++j) {
         const int k = KPL * lane + j;
         AKnot& Kj = K[j];
-        Kj.m = 0;
-        Kj.gm = Kj.drop = Kj.add = 0;
-        Kj.r0 = Kj.r1 = Kj.x0 = Kj.x1 = Kj.w = Kj.be = 0.0;
-        Kj.rh0 = Kj.rh1 = Kj.d0 = Kj.d1 = Kj.qx0 = Kj.qx1 = 0.0;
-        Kj.P00 = Kj.P01 = Kj.P11 = Kj.h00 = Kj.h01 = Kj.h11 = 0.0;
-        Kj.rr0 = Kj.rr1 = Kj.xr0 = Kj.xr1 = 0.0;
+        knot_zero(Kj);
         if (k < N) {
             const int64_t st = p * N + k;
             const KnotIn in = knot_in<PH>(p, k, N, omega, xi_ref, vrp_ref, nfacets, ps, sPh);
@@ -1720,7 +1668,6 @@ __global__ __launch_bounds__(kWave, 2) void dcm_mpc_warm_kernel(
         certified = as_passes<KPL, TR, double>(K, Pd, R, NH, N, lane, xi00, xi01, pk, pl, 10, 4, -1, npass);
         AS_STAMP_ADD(14, t_b);
     }
-#if BLF_WARM_RETRY
     // the warm passes did not certify: the QP is solved again from a cold start (fp32 search,
     // fp64 passes), and if that hands it over, stage 2 starts it cold (kPendingCold)
     if (!certified && status == 0) {
@@ -1728,7 +1675,6 @@ __global__ __launch_bounds__(kWave, 2) void dcm_mpc_warm_kernel(
         __syncthreads();   // the LDS is the cold solve's
         goto cold;
     }
-#endif
     AS_STAMP(t_out);
 
     as_write_outputs<KPL, LAMOUT>(K, pk, pl, certified, status, p, N, M, lane, xi00, xi01, xi_out, vrp_out,
@@ -1760,19 +1706,31 @@ cold:
 constexpr int64_t kFusedMaxBatch = 1024;
 constexpr int64_t kDppTreeMaxBatch = BLF_DPP_TREE_MAX_BATCH;
 
+// The cold or warm kernel of a launch, by multipliers out (lam), phase-indexed input (ph) and
+// scan tree D.
+template <bool WARM, int KPL, int MF, bool L, bool H, int D>
+constexpr auto as_kernel_of()
+{
+    if constexpr (WARM) return dcm_mpc_warm_kernel<KPL, L, H, D, MF>;
+    else return dcm_mpc_cold_kernel<KPL, L, H, D, MF>;
+}
+
+template <bool WARM, int KPL, int MF, int D>
+auto as_kernel(bool lam, bool ph)
+{
+    return ph ? (lam ? as_kernel_of<WARM, KPL, MF, true, true, D>() : as_kernel_of<WARM, KPL, MF, false, true, D>())
+              : (lam ? as_kernel_of<WARM, KPL, MF, true, false, D>() : as_kernel_of<WARM, KPL, MF, false, false, D>());
+}
+
 template <int KPL, int MF>
 blf_status launch_kpl(const KParams& kp, const blf_dcm_mpc_problem* pb, const blf_dcm_mpc_warm_start* warm,
                       int64_t batch, const blf_dcm_mpc_solution* sol, double* lam_out, hipStream_t s,
                       const PhaseSrc* ps, bool* stage2_done)
 {
-#ifndef AS_EXTRA_LDS
-#define AS_EXTRA_LDS 0
-#endif
     const size_t slots = (size_t)kp.M * (KPL * ((kp.N + KPL - 1) / KPL));
     const PhaseSrc none{};
     const PhaseSrc& src = ps ? *ps : none;
-    const size_t lds = 3 * sizeof(double) * slots +
-                       (ps ? ph_lds_bytes(ps->P, kp.N) : 0) + AS_EXTRA_LDS;
+    const size_t lds = 3 * sizeof(double) * slots + (ps ? ph_lds_bytes(ps->P, kp.N) : 0);
     if (lds > 64 * 1024)
         return set_error(BLF_ERR_UNSUPPORTED, "active-set kernel: %zu B of LDS (%d phases)", lds, ps ? ps->P : 0);
     // the scan tree: DPP for small batches with one knot per lane (the oracle's as_tree follows the
@@ -1793,23 +1751,15 @@ blf_status launch_kpl(const KParams& kp, const blf_dcm_mpc_problem* pb, const bl
         return check_hip(hipGetLastError(), "dcm_mpc_cold_fused_kernel launch");
     }
     if (warm == nullptr) {
-#define AS_COLD(L, H, D) dcm_mpc_cold_kernel<KPL, L, H, D, MF>
-#define AS_COLD_TR(D) (ps ? (lam_out ? AS_COLD(true, true, D) : AS_COLD(false, true, D)) \
-                          : (lam_out ? AS_COLD(true, false, D) : AS_COLD(false, false, D)))
-        auto kern = tr == kAltTree ? AS_COLD_TR(kAltTree) : AS_COLD_TR(kTreeKS);
-#undef AS_COLD_TR
-#undef AS_COLD
+        auto kern = tr == kAltTree ? as_kernel<false, KPL, MF, kAltTree>(lam_out != nullptr, ps != nullptr)
+                                   : as_kernel<false, KPL, MF, kTreeKS>(lam_out != nullptr, ps != nullptr);
         hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, kp,
                            pb->xi_init, pb->omega, pb->xi_ref, pb->vrp_ref, pb->A, pb->b, pb->nfacets, sol->xi,
                            sol->vrp, sol->status, sol->iters, sol->polished, lam_out, src);
         return check_hip(hipGetLastError(), "dcm_mpc_cold_kernel launch");
     }
-#define AS_WARM(L, H, D) dcm_mpc_warm_kernel<KPL, L, H, D, MF>
-#define AS_WARM_TR(D) (ps ? (lam_out ? AS_WARM(true, true, D) : AS_WARM(false, true, D)) \
-                          : (lam_out ? AS_WARM(true, false, D) : AS_WARM(false, false, D)))
-    auto kern = tr == kAltTree ? AS_WARM_TR(kAltTree) : AS_WARM_TR(kTreeKS);
-#undef AS_WARM_TR
-#undef AS_WARM
+    auto kern = tr == kAltTree ? as_kernel<true, KPL, MF, kAltTree>(lam_out != nullptr, ps != nullptr)
+                               : as_kernel<true, KPL, MF, kTreeKS>(lam_out != nullptr, ps != nullptr);
     hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, kp,
                        pb->xi_init, pb->omega, pb->xi_ref, pb->vrp_ref, pb->A, pb->b, pb->nfacets, warm->vrp,
                        warm->lambda, sol->xi, sol->vrp, sol->status, sol->iters, sol->polished, lam_out, src);

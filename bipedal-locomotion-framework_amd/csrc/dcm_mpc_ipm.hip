@@ -30,7 +30,7 @@ namespace {
 using namespace qp;
 
 template <int NT, bool WARM, bool LAMOUT, int MF>
-__global__ __launch_bounds__(NT, (NT <= 256 ? BLF_MIN_WAVES : 1)) void dcm_mpc_ipm_kernel(
+__global__ __launch_bounds__(NT, (NT <= 256 ? kIpmMinWaves : 1)) void dcm_mpc_ipm_kernel(
     KParams P, const double* __restrict__ xi_init, const double* __restrict__ omega,
     const double* __restrict__ xi_ref, const double* __restrict__ vrp_ref,
     const double* __restrict__ Ain, const double* __restrict__ bin,
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(NT, (NT <= 256 ? BLF_MIN_WAVES : 1)) void dcm_mpc_i
 // at 168 VGPRs stored 12.5 KB of register spills per QP on its way to the status check).
 // Workgroup 0 zeroes the other count slot, the one the stream's next solve appends to.
 template <int NT, bool WARM, bool LAMOUT, int MF>
-__global__ __launch_bounds__(NT, (NT <= 256 ? BLF_MIN_WAVES : 1)) void dcm_mpc_ipm_list_kernel(
+__global__ __launch_bounds__(NT, (NT <= 256 ? kIpmMinWaves : 1)) void dcm_mpc_ipm_list_kernel(
     KParams P, const double* __restrict__ xi_init, const double* __restrict__ omega,
     const double* __restrict__ xi_ref, const double* __restrict__ vrp_ref,
     const double* __restrict__ Ain, const double* __restrict__ bin,

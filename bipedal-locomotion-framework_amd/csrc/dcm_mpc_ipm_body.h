@@ -589,9 +589,6 @@ __device__ __forceinline__ void solve(const KN& K, double g0, double g1, double*
 // of the least B-distance winning (oracle sat_project's candidate order).  Leaves r, xi, s, lam,
 // the residuals and xb in place; returns mu, pres, dres, and false on a lane whose LQ factorization
 // failed.
-#ifndef BLF_SAT_ON
-#define BLF_SAT_ON 1
-#endif
 constexpr int kBS = 12;   // bnd slot: the rollout's xi at the end of wavefront w
 template <int NW, class KN>
 __device__ __forceinline__ bool sat_start(KN& K, const KParams& P, const Lds& L, Reduce<NW>& R, double* bnd,
@@ -795,11 +792,9 @@ __device__ __forceinline__ bool sat_start(KN& K, const KParams& P, const Lds& L,
     return ok;
 }
 
-#ifndef BLF_MIN_WAVES
 // waves per SIMD the register allocation must allow: 2 (<= 256 VGPRs).  At 3 (<= 168) the polish
 // and the saturated start spill 89-118 VGPRs and ~210 B of scratch per lane (round 4).
-#define BLF_MIN_WAVES 2
-#endif
+constexpr int kIpmMinWaves = 2;
 // The solve of QP p by one workgroup of NT threads (the kernel below; the active-set kernel's
 // fused stage 2 for N <= 64, dcm_mpc_as.hip, calls it from its own 64-thread workgroup).
 template <int NT, bool WARM, bool LAMOUT, int MF = kMaxFacets>
@@ -1027,7 +1022,7 @@ __device__ __forceinline__ void ipm_solve(
         bool sat_pending = P.tol_polish > 0.0 && P.stage2;
         double last_a = 1.0;   // the previous IPM step length (the stalled-step polish, kStallStep)
         for (it = 0; status == 0; ++it) {
-            if (BLF_SAT_ON && sat_pending) {
+            if (sat_pending) {
                 sat_pending = false;
                 STAMP(t_sat);   // (stamp builds: the saturated start counts as start-up, slot 12)
                 const bool oks = sat_start<NW>(K, P, L, R, bnd, N, nwa, k, wv, lane, own, last, mmax, xi00, xi01,

@@ -216,11 +216,8 @@ __global__ __launch_bounds__(256) void lti_dynamics_rows_kernel(int n, int m,
 // of loads per lane, 16 B each on full aligned chunks), transposed through LDS; the recurrence
 // runs lane-per-problem and the xi chunk leaves through LDS the same way.  (Prefetching the next
 // chunk during the recurrence measured no faster and cost 96 VGPRs.)
-#ifndef BLF_ROLL_KC
-#define BLF_ROLL_KC 32
-#endif
-constexpr int KC = BLF_ROLL_KC;   // knots per chunk: 64 x 98 x 8 B of LDS per wave (16: 12 % slower,
-                                  // per-chunk overhead; 50: the register chunk spills)
+constexpr int KC = 32;   // knots per chunk: 64 x 98 x 8 B of LDS per wave (16: 12 % slower,
+                         // per-chunk overhead; 50: the register chunk spills)
 constexpr int kRollSw = 2 * KC + 1;   // padded LDS row of the vrp / xi chunk
 
 struct RollChunk {
@@ -441,10 +438,7 @@ __global__ __launch_bounds__(64) void dcm_rollout_rows_kernel(const double* __re
     slab_store<64, 16>(xi_out + p0 * 2 * (N + 1), 2 * (N + 1), s_x, SWx, np, 2 * (N + 1));
 }
 
-#ifndef BLF_ROLL_PPW
-#define BLF_ROLL_PPW 8
-#endif
-constexpr int kRollPPW = BLF_ROLL_PPW;
+constexpr int kRollPPW = 8;   // problems per wavefront of dcm_rollout_rows_kernel
 inline int odd_stride_host(int w) { return w | 1; }
 
 }  // namespace

@@ -29,15 +29,9 @@ constexpr int kHullBlock = 64;
 // eight facets of a polygon that phase 2 reads in one lane group hit distinct banks (a stride of
 // 64 put all eight on one bank: 8-way), and the Y array's 2-double offset interleaves the
 // staging stores of X and Y (16-way on one bank pair before: 13 % of the wave's cycles).
-#ifndef BLF_HULL_PAD
-#define BLF_HULL_PAD 1
-#endif
-constexpr int kHullStride = BLF_HULL_PAD ? 68 : 64;   // BLF_HULL_PAD=0: the unpadded layout (A/B)
-constexpr int kHullYOff = BLF_HULL_PAD ? 2 : 0;
-#ifndef BLF_HULL_U
-#define BLF_HULL_U 8
-#endif
-constexpr int HU = BLF_HULL_U;   // facet pairs per lane in flight (phase 2)
+constexpr int kHullStride = 68;
+constexpr int kHullYOff = 2;
+constexpr int HU = 8;   // facet pairs per lane in flight (phase 2)
 
 __device__ __forceinline__ double cross3(double ox, double oy, double ax, double ay, double bx,
                                          double by)
@@ -74,10 +68,7 @@ __device__ __forceinline__ int hull2d_rows(int64_t batch, int64_t p0)
 // only on a pop).  Phase 2 (after a barrier): consecutive threads take consecutive (polygon, facet) pairs,
 // compute the facet once and store A as 16-B and b as 8-B coalesced writes.
 template <bool PK>
-#ifndef BLF_HULL_MINWAVES   // waves per SIMD the register allocation must allow (A/B builds)
-#define BLF_HULL_MINWAVES 1
-#endif
-__global__ __launch_bounds__(kHullBlock, BLF_HULL_MINWAVES) void hull2d_kernel(const double* __restrict__ pts,
+__global__ __launch_bounds__(kHullBlock, 1) void hull2d_kernel(const double* __restrict__ pts,
                                                             const int32_t* __restrict__ npts,
                                                             int32_t P, int32_t M, int64_t batch,
                                                             double* __restrict__ Aout,
@@ -546,17 +537,8 @@ __global__ __launch_bounds__(256) void quintic_fit_kernel(const double* __restri
 
 // one lane per (spline, query); the workgroup's [256][3][D] output slab is staged in LDS and
 // written with coalesced 16-B stores (slab.h)
-#ifndef BLF_Q_BLOCK   // queries per workgroup (A/B builds)
-#define BLF_Q_BLOCK 256
-#endif
-constexpr int kEvalBlock = BLF_Q_BLOCK;
-#ifndef BLF_Q_STAGE
-#define BLF_Q_STAGE 512
-#endif
-constexpr int kEvalStage = BLF_Q_STAGE;
-#ifndef BLF_Q_DIRECT
-#define BLF_Q_DIRECT 0
-#endif   // doubles of staged spline data per workgroup (4 KB)
+constexpr int kEvalBlock = 256;   // queries per workgroup
+constexpr int kEvalStage = 512;   // doubles of staged spline data per workgroup (4 KB)
 
 template <bool VEC>
 __global__ __launch_bounds__(kEvalBlock) void quintic_eval_kernel(const double* __restrict__ kt,
@@ -632,19 +614,11 @@ __global__ __launch_bounds__(kEvalBlock) void quintic_eval_kernel(const double* 
             const double p = c0 + tau * (c1 + tau * (c2 + tau * (c3 + tau * (c4 + tau * c5))));
             const double v = c1 + tau * (2.0 * c2 + tau * (3.0 * c3 + tau * (4.0 * c4 + tau * (5.0 * c5))));
             const double a = 2.0 * c2 + tau * (6.0 * c3 + tau * (12.0 * c4 + tau * (20.0 * c5)));
-            if (BLF_Q_DIRECT) {   // A/B: the lane's own row straight to HBM (plain stores)
-                double* og = pva + gid * W;
-                og[d] = p;
-                og[D + d] = v;
-                og[2 * D + d] = a;
-            } else {
-                o[d] = p;
-                o[D + d] = v;
-                o[2 * D + d] = a;
-            }
+            o[d] = p;
+            o[D + d] = v;
+            o[2 * D + d] = a;
         }
     }
-    if (BLF_Q_DIRECT) return;
     __syncthreads();
     slab_store<kEvalBlock, 6>(pva + g0 * W, W, s_out, SW, rows, W);   // 9 doubles x 256: one batch
 }

@@ -14,10 +14,6 @@
 // next load serialises on HBM latency (the first version of dcm_rollout_kernel: 0.65 ms, 20 %
 // of the HBM roofline).
 #pragma once
-#ifndef BLF_NT_STORE
-#define BLF_NT_STORE 1
-#endif
-
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,37 +21,25 @@ namespace blf {
 
 // A 16-B store of a streamed output (written once, not re-read by the kernel): non-temporal, so
 // the output stream does not displace the inputs from the caches (the write-dominated quintic
-// evaluation: 0.773 -> 0.731 ms; reads and the other kernels unchanged).  BLF_NT_STORE=0: plain.
+// evaluation: 0.773 -> 0.731 ms; reads and the other kernels unchanged).
 __device__ __forceinline__ void st_stream(double2* p, double2 v)
 {
-#if BLF_NT_STORE
     typedef double d2v __attribute__((ext_vector_type(2)));
     d2v w;
     w.x = v.x;
     w.y = v.y;
     __builtin_nontemporal_store(w, reinterpret_cast<d2v*>(p));
-#else
-    *p = v;
-#endif
 }
 
 // The same for 8-B / 4-B streamed outputs (phase expansion's offsets and facet counts).
 __device__ __forceinline__ void st_stream(double* p, double v)
 {
-#if BLF_NT_STORE
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 __device__ __forceinline__ void st_stream(int32_t* p, int32_t v)
 {
-#if BLF_NT_STORE
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 // A streamed output stored non-temporally (NT) or plainly, chosen per launch by the output's size.

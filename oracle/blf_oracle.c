@@ -609,9 +609,7 @@ double orc_wave_tree_sum(const double* c, int n)
 }
 
 #define MF 16   /* facet slots (max_facets <= 16) */
-#ifndef ORC_GUESS_PASSES
 #define ORC_GUESS_PASSES 8    /* active-set start: drop/add passes (kernel: kGuessPasses) */
-#endif
 #define ORC_TOL_DUAL_REL 1e-3   /* the certificate's relative dual tolerance (kernel kTolDualRel) */
 #define ORC_LAM_REL 1e-8        /* the IPM polish's guess: lam_i >= this x the knot's largest (kernel kLamRel) */
 #define ORC_LAM_REL_CROSS 0.3   /* ... among facets this close to parallel to the largest one's (kernel kLamRelCross) */
@@ -1072,11 +1070,6 @@ static double dcm_residuals(dcm_ws* w, int use_facets)
  * (the structure-preserving doubling composition: only (I + G H)^{-1}, eigenvalues >= 1). */
 typedef struct { double a[4], g[3], h[3]; } rc_el;
 
-/* the kernel's BLF_RC_FORM (dcm_qp_common.h): where 1 / det(I + G H) enters the products */
-#ifndef ORC_RC_FORM
-#define ORC_RC_FORM 2
-#endif
-
 static int rc_combine(rc_el* e1, const rc_el* e2)
 {
     const double* A1 = e1->a; const double* G1 = e1->g; const double* H1 = e1->h;
@@ -1088,83 +1081,39 @@ static int rc_combine(rc_el* e1, const rc_el* e2)
     const double detT = fma(T00, T11, -(T01 * T10));
     const int ok = (detT > 0.0) && !isinf(detT);
     const double it = 1.0 / detT;
-#if ORC_RC_FORM >= 2
-    {
-        /* adj(T) = [T11, -T01; -T10, T00]: the products run beside the division (rc_combine of
-         * dcm_qp_common.h, BLF_RC_FORM) */
-        const double Up00 = FD2(T11, A1[0], -T01, A1[2]);
-        const double Up01 = FD2(T11, A1[1], -T01, A1[3]);
-        const double Up10 = FD2(-T10, A1[0], T00, A1[2]);
-        const double Up11 = FD2(-T10, A1[1], T00, A1[3]);
-        const double Vp00 = FD2(A2[0], T11, A2[1], -T10);
-        const double Vp01 = FD2(A2[0], -T01, A2[1], T00);
-        const double Vp10 = FD2(A2[2], T11, A2[3], -T10);
-        const double Vp11 = FD2(A2[2], -T01, A2[3], T00);
-        const double Xp00 = FD2(Vp00, G1[0], Vp01, G1[1]);
-        const double Xp01 = FD2(Vp00, G1[1], Vp01, G1[2]);
-        const double Xp10 = FD2(Vp10, G1[0], Vp11, G1[1]);
-        const double Xp11 = FD2(Vp10, G1[1], Vp11, G1[2]);
-        const double Y00 = FD2(H2[0], A1[0], H2[1], A1[2]);
-        const double Y01 = FD2(H2[0], A1[1], H2[1], A1[3]);
-        const double Y10 = FD2(H2[1], A1[0], H2[2], A1[2]);
-        const double Y11 = FD2(H2[1], A1[1], H2[2], A1[3]);
-        const double gp0 = FD2(Xp00, A2[0], Xp01, A2[1]);
-        const double gp1 = FD2(Xp00, A2[2], Xp01, A2[3]);
-        const double gp2 = FD2(Xp10, A2[2], Xp11, A2[3]);
-        rc_el r;
-#if ORC_RC_FORM == 2
-        const double U00 = Up00 * it, U01 = Up01 * it, U10 = Up10 * it, U11 = Up11 * it;
-        r.a[0] = FD2(A2[0], U00, A2[1], U10);
-        r.a[1] = FD2(A2[0], U01, A2[1], U11);
-        r.a[2] = FD2(A2[2], U00, A2[3], U10);
-        r.a[3] = FD2(A2[2], U01, A2[3], U11);
-        r.h[0] = FD3(U00, Y00, U10, Y10, H1[0]);
-        r.h[1] = FD3(U00, Y01, U10, Y11, H1[1]);
-        r.h[2] = FD3(U01, Y01, U11, Y11, H1[2]);
-#else
-        r.a[0] = FD2(A2[0], Up00, A2[1], Up10) * it;
-        r.a[1] = FD2(A2[0], Up01, A2[1], Up11) * it;
-        r.a[2] = FD2(A2[2], Up00, A2[3], Up10) * it;
-        r.a[3] = FD2(A2[2], Up01, A2[3], Up11) * it;
-        r.h[0] = fma(FD2(Up00, Y00, Up10, Y10), it, H1[0]);
-        r.h[1] = fma(FD2(Up00, Y01, Up10, Y11), it, H1[1]);
-        r.h[2] = fma(FD2(Up01, Y01, Up11, Y11), it, H1[2]);
-#endif
-        r.g[0] = fma(gp0, it, G2[0]);
-        r.g[1] = fma(gp1, it, G2[1]);
-        r.g[2] = fma(gp2, it, G2[2]);
-        *e1 = r;
-        return ok;
-    }
-#endif
-    const double Ti00 = T11 * it, Ti01 = -(T01 * it), Ti10 = -(T10 * it), Ti11 = T00 * it;
-    const double U00 = FD2(Ti00, A1[0], Ti01, A1[2]);
-    const double U01 = FD2(Ti00, A1[1], Ti01, A1[3]);
-    const double U10 = FD2(Ti10, A1[0], Ti11, A1[2]);
-    const double U11 = FD2(Ti10, A1[1], Ti11, A1[3]);
-    const double V00 = FD2(A2[0], Ti00, A2[1], Ti10);
-    const double V01 = FD2(A2[0], Ti01, A2[1], Ti11);
-    const double V10 = FD2(A2[2], Ti00, A2[3], Ti10);
-    const double V11 = FD2(A2[2], Ti01, A2[3], Ti11);
-    const double X00 = FD2(V00, G1[0], V01, G1[1]);
-    const double X01 = FD2(V00, G1[1], V01, G1[2]);
-    const double X10 = FD2(V10, G1[0], V11, G1[1]);
-    const double X11 = FD2(V10, G1[1], V11, G1[2]);
+    /* adj(T) = [T11, -T01; -T10, T00]: the products run beside the division (rc_combine of
+     * dcm_qp_common.h); U = adj(T) A1 and the G block are scaled by 1 / det at the end */
+    const double Up00 = FD2(T11, A1[0], -T01, A1[2]);
+    const double Up01 = FD2(T11, A1[1], -T01, A1[3]);
+    const double Up10 = FD2(-T10, A1[0], T00, A1[2]);
+    const double Up11 = FD2(-T10, A1[1], T00, A1[3]);
+    const double Vp00 = FD2(A2[0], T11, A2[1], -T10);
+    const double Vp01 = FD2(A2[0], -T01, A2[1], T00);
+    const double Vp10 = FD2(A2[2], T11, A2[3], -T10);
+    const double Vp11 = FD2(A2[2], -T01, A2[3], T00);
+    const double Xp00 = FD2(Vp00, G1[0], Vp01, G1[1]);
+    const double Xp01 = FD2(Vp00, G1[1], Vp01, G1[2]);
+    const double Xp10 = FD2(Vp10, G1[0], Vp11, G1[1]);
+    const double Xp11 = FD2(Vp10, G1[1], Vp11, G1[2]);
     const double Y00 = FD2(H2[0], A1[0], H2[1], A1[2]);
     const double Y01 = FD2(H2[0], A1[1], H2[1], A1[3]);
     const double Y10 = FD2(H2[1], A1[0], H2[2], A1[2]);
     const double Y11 = FD2(H2[1], A1[1], H2[2], A1[3]);
+    const double gp0 = FD2(Xp00, A2[0], Xp01, A2[1]);
+    const double gp1 = FD2(Xp00, A2[2], Xp01, A2[3]);
+    const double gp2 = FD2(Xp10, A2[2], Xp11, A2[3]);
     rc_el r;
+    const double U00 = Up00 * it, U01 = Up01 * it, U10 = Up10 * it, U11 = Up11 * it;
     r.a[0] = FD2(A2[0], U00, A2[1], U10);
     r.a[1] = FD2(A2[0], U01, A2[1], U11);
     r.a[2] = FD2(A2[2], U00, A2[3], U10);
     r.a[3] = FD2(A2[2], U01, A2[3], U11);
-    r.g[0] = FD3(X00, A2[0], X01, A2[1], G2[0]);
-    r.g[1] = FD3(X00, A2[2], X01, A2[3], G2[1]);
-    r.g[2] = FD3(X10, A2[2], X11, A2[3], G2[2]);
     r.h[0] = FD3(U00, Y00, U10, Y10, H1[0]);
     r.h[1] = FD3(U00, Y01, U10, Y11, H1[1]);
     r.h[2] = FD3(U01, Y01, U11, Y11, H1[2]);
+    r.g[0] = fma(gp0, it, G2[0]);
+    r.g[1] = fma(gp1, it, G2[1]);
+    r.g[2] = fma(gp2, it, G2[2]);
     *e1 = r;
     return ok;
 }
@@ -1180,35 +1129,18 @@ static int rc_apply(const rc_el* e, double P00, double P01, double P11, double* 
     const double detS = fma(S00, S11, -(S01 * S10));
     const int ok = (detS > 0.0) && !isinf(detS);
     const double is = 1.0 / detS;
-#if ORC_RC_FORM >= 1
-    {
-        /* W' = P adj(S), Z' = W' A, out = (A^T Z') / det(S) + H (rc_apply, BLF_RC_FORM) */
-        const double Wp00 = FD2(P00, S11, P01, -S10);
-        const double Wp01 = FD2(P00, -S01, P01, S00);
-        const double Wp10 = FD2(P01, S11, P11, -S10);
-        const double Wp11 = FD2(P01, -S01, P11, S00);
-        const double Zp00 = FD2(Wp00, A[0], Wp01, A[2]);
-        const double Zp01 = FD2(Wp00, A[1], Wp01, A[3]);
-        const double Zp10 = FD2(Wp10, A[0], Wp11, A[2]);
-        const double Zp11 = FD2(Wp10, A[1], Wp11, A[3]);
-        out[0] = fma(FD2(A[0], Zp00, A[2], Zp10), is, H[0]);
-        out[1] = fma(FD2(A[0], Zp01, A[2], Zp11), is, H[1]);
-        out[2] = fma(FD2(A[1], Zp01, A[3], Zp11), is, H[2]);
-        return ok;
-    }
-#endif
-    const double Si00 = S11 * is, Si01 = -(S01 * is), Si10 = -(S10 * is), Si11 = S00 * is;
-    const double W00 = FD2(P00, Si00, P01, Si10);
-    const double W01 = FD2(P00, Si01, P01, Si11);
-    const double W10 = FD2(P01, Si00, P11, Si10);
-    const double W11 = FD2(P01, Si01, P11, Si11);
-    const double Z00 = FD2(W00, A[0], W01, A[2]);
-    const double Z01 = FD2(W00, A[1], W01, A[3]);
-    const double Z10 = FD2(W10, A[0], W11, A[2]);
-    const double Z11 = FD2(W10, A[1], W11, A[3]);
-    out[0] = FD3(A[0], Z00, A[2], Z10, H[0]);
-    out[1] = FD3(A[0], Z01, A[2], Z11, H[1]);
-    out[2] = FD3(A[1], Z01, A[3], Z11, H[2]);
+    /* W' = P adj(S), Z' = W' A, out = (A^T Z') / det(S) + H (rc_apply of dcm_qp_common.h) */
+    const double Wp00 = FD2(P00, S11, P01, -S10);
+    const double Wp01 = FD2(P00, -S01, P01, S00);
+    const double Wp10 = FD2(P01, S11, P11, -S10);
+    const double Wp11 = FD2(P01, -S01, P11, S00);
+    const double Zp00 = FD2(Wp00, A[0], Wp01, A[2]);
+    const double Zp01 = FD2(Wp00, A[1], Wp01, A[3]);
+    const double Zp10 = FD2(Wp10, A[0], Wp11, A[2]);
+    const double Zp11 = FD2(Wp10, A[1], Wp11, A[3]);
+    out[0] = fma(FD2(A[0], Zp00, A[2], Zp10), is, H[0]);
+    out[1] = fma(FD2(A[0], Zp01, A[2], Zp11), is, H[1]);
+    out[2] = fma(FD2(A[1], Zp01, A[3], Zp11), is, H[2]);
     return ok;
 }
 
@@ -2174,9 +2106,6 @@ int orc_dcm_mpc_solve(const orc_dcm_params* prm, const double* xi_init, const do
                                   xi, vrp, NULL, iters_out, NULL, NULL);
 }
 
-#ifndef ORC_WARM_RETRY
-#define ORC_WARM_RETRY 1   /* BLF_WARM_RETRY */
-#endif
 int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, const double* omega,
                            const double* xi_ref, const double* vrp_ref, const double* Ain,
                            const double* bin, const int32_t* nfacets, const orc_dcm_warm* warm,
@@ -2347,8 +2276,8 @@ int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, con
         if (as_kernel) as_passes = w->npass;   /* the warm kernel's passes */
         free(gm);
         if (okg) { polished = 1; status = 0; it = 0; goto done; }
-        if (ORC_WARM_RETRY && warm && as_kernel) {
-            /* the warm kernel's cold re-solve (csrc/dcm_mpc_as.hip, BLF_WARM_RETRY): a QP its warm
+        if (warm && as_kernel) {
+            /* the warm kernel's cold re-solve (dcm_mpc_warm_kernel, csrc/dcm_mpc_as.hip): a QP its warm
              * passes do not certify is solved again from a cold start (fp32 search, fp64 passes),
              * and the interior point method, if it still needs it, starts cold (kPendingCold) */
             free(mem);

@@ -63,7 +63,7 @@ def test_c5_device_window_r05_bitwise(handle, oracle):
     """tests/golden/c5_device_windows_r05.npz: the window of the device's own c5 trajectory (round 5,
     robot 13356 at period 22 of rank 0's shard, tools/capture_c5_failures.py) whose warm start
     needed 92 interior point iterations -- past the default cap of 50.  The warm kernel's passes do
-    not certify it, so it is solved again from a cold start (BLF_WARM_RETRY) and stage 2 starts cold
+    not certify it, so it is solved again from a cold start (the warm kernel's retry) and stage 2 starts cold
     (kPendingCold): 31 iterations in round 5, 22 with the round-6 polish rules.  Device and oracle
     bit for bit, certified."""
     prob, d = _load("c5_device_windows_r05.npz")

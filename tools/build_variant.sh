@@ -1,7 +1,7 @@
 #!/bin/bash
 # Diagnostics: build the working copy of one kernel source (VSRC, default dcm_mpc_ipm; plus extra
 # hipcc flags) into lib/libblf_<name>.so next to the product library, for A/B runs with
-# tools/sessions/ab_multi.sh.
+# tools/gpu_ab_libs.sh (the c2 batch) or tools/ab_c5_libs.sh (the c5 closed loop).
 #   [VSRC=dcm_mpc_as] tools/build_variant.sh <name> [hipcc flags...]
 set -eu
 cd "$(dirname "$0")/../bipedal-locomotion-framework_amd"
