@@ -29,7 +29,8 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_contact_model_eval", "blf_contact_point_wrench", "blf_fbk_dynamics",
             "blf_fbk_euler_integrate", "blf_fbd_dynamics", "blf_fbd_euler_integrate",
             "blf_fb_dcm", "blf_dcm_posture_reference", "blf_fbd_euler_integrate_impedance",
-            "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance"]
+            "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance",
+            "blf_swing_foot_eval", "blf_so3_eval"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -73,7 +74,16 @@ class JointImpedance(ctypes.Structure):
     _fields_ = [("ndof", _i32), ("reserved", _i32), ("kp", _vp), ("kd", _vp), ("q_ref", _vp)]
 
 
-FB_STATE_KEYS = ("base_vel", "joint_vel", "base_pos", "base_rot", "joint_pos")
+class SwingFootParams(ctypes.Structure):
+    """blf_swing_foot_params (include/blf/blf_c.h section 11)."""
+    _fields_ = [("max_contacts", _i32), ("reserved", _i32), ("step_height", _f64),
+                ("apex_ratio", _f64), ("landing_velocity", _f64), ("landing_acceleration", _f64)]
+
+
+SWING_OUTPUTS = ("pose", "twist", "accel", "contact_idx", "in_contact")
+SO3_OUTPUTS = ("rot", "omega", "alpha")
+
+FB_STATE_KEYS =("base_vel", "joint_vel", "base_pos", "base_rot", "joint_pos")
 
 
 class BlfError(RuntimeError):
@@ -201,6 +211,9 @@ def lib():
                                       _i64, _vp]
         L.blf_contact_rls_advance.argtypes = [_vp, _f64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp,
                                               _i32, _vp, _vp, _i64, _vp]
+        L.blf_swing_foot_eval.argtypes = [_vp, ctypes.POINTER(SwingFootParams), _vp, _vp, _vp, _i64,
+                                          _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.blf_so3_eval.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]
         L.blf_dcm_mpc_flops_per_iter.restype = _f64
         L.blf_set_qp_launch_mode.argtypes = [_i32, _i32]
         for name in EXPORTED:
@@ -762,6 +775,58 @@ class Handle:
             _ptr(state, torch.float64, (B, 2), "state"),
             _ptr(covariance, torch.float64, (B, 2, 2), "covariance"), B, _stream(stream)))
         return state, covariance
+
+    # ---- Planners::SwingFootPlanner / SO3Planner, batched ------------------------------------
+    def swing_foot_eval(self, contact_pose, contact_time, ncontacts, tq, step_height=0.05,
+                        apex_ratio=0.5, landing_velocity=0.0, landing_acceleration=0.0,
+                        outputs=SWING_OUTPUTS, out=None, stream=None):
+        """SE(3) swing-foot trajectories (blf_swing_foot_eval): contact_pose [L,C,12], contact_time
+        [L,C,2] = (activation, deactivation), ncontacts [L] int32, tq [L,Q].  Returns a dict of the
+        requested outputs: pose [L,Q,12], twist / accel [L,Q,6], contact_idx / in_contact [L,Q]
+        int32 (out: tensors to write into instead of new ones)."""
+        torch = _torch()
+        L, C = contact_pose.shape[0], contact_pose.shape[1]
+        Q = tq.shape[1]
+        prm = SwingFootParams(C, 0, float(step_height), float(apex_ratio), float(landing_velocity),
+                              float(landing_acceleration))
+        shapes = dict(pose=(L, Q, 12), twist=(L, Q, 6), accel=(L, Q, 6), contact_idx=(L, Q),
+                      in_contact=(L, Q))
+        res, ptrs = {}, []
+        for k in SWING_OUTPUTS:
+            if k not in outputs:
+                ptrs.append(None)
+                continue
+            dt = torch.int32 if k in ("contact_idx", "in_contact") else torch.float64
+            res[k] = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=dt,
+                                                                             device=tq.device)
+            ptrs.append(_ptr(res[k], dt, shapes[k], k))
+        _check(lib().blf_swing_foot_eval(
+            self._h, ctypes.byref(prm), _ptr(contact_pose, torch.float64, (L, C, 12), "contact_pose"),
+            _ptr(contact_time, torch.float64, (L, C, 2), "contact_time"),
+            _ptr(ncontacts, torch.int32, (L,), "ncontacts"), L, _ptr(tq, torch.float64, (L, Q), "tq"),
+            Q, *ptrs, _stream(stream)))
+        return res
+
+    def so3_eval(self, R0, R1, duration, tq, outputs=SO3_OUTPUTS, out=None, stream=None):
+        """Minimum-jerk SO(3) trajectories (blf_so3_eval): R0, R1 [S,3,3] or [S,9], duration [S],
+        tq [S,Q] (clamped to [0, duration]).  Returns a dict of rot [S,Q,9], omega, alpha [S,Q,3]."""
+        torch = _torch()
+        S, Q = tq.shape
+        R0, R1 = R0.reshape(S, 9), R1.reshape(S, 9)
+        shapes = dict(rot=(S, Q, 9), omega=(S, Q, 3), alpha=(S, Q, 3))
+        res, ptrs = {}, []
+        for k in SO3_OUTPUTS:
+            if k not in outputs:
+                ptrs.append(None)
+                continue
+            res[k] = out[k] if out is not None and k in out else torch.empty(
+                shapes[k], dtype=torch.float64, device=tq.device)
+            ptrs.append(_ptr(res[k], torch.float64, shapes[k], k))
+        _check(lib().blf_so3_eval(
+            self._h, _ptr(R0, torch.float64, (S, 9), "R0"), _ptr(R1, torch.float64, (S, 9), "R1"),
+            _ptr(duration, torch.float64, (S,), "duration"), S, _ptr(tq, torch.float64, (S, Q), "tq"),
+            Q, *ptrs, _stream(stream)))
+        return res
 
     def fbk_dynamics(self, rho, rot, twist, joint_vel, stream=None):
         """FloatingBaseSystemKinematics::dynamics: rot [B,3,3], twist [B,6], joint_vel [B,n]."""

@@ -200,6 +200,36 @@ def swing_splines(prob, apex_height=0.05, queries=32):
             np.ascontiguousarray(np.concatenate(tq)))
 
 
+def foot_contact_tables(prob):
+    """The contact lists of a make_batch problem as blf_swing_foot_eval's tables.
+
+    Returns {"left": t, "right": t} with t = dict(contact_pose [B, C, 12], contact_time [B, C, 2],
+    ncontacts [B] int32), both feet padded to a common C (padding rows are zero and never read).
+    Times come from the knot schedule as `index * dt` (activation, deactivation); a contact's pose
+    is (x, y, 0) with Rz(yaw), row-major.
+    """
+    lists, dt, poses = prob["schedule"], prob["dt"], prob["poses"]
+    B = poses.shape[0]
+    C = max(len(lists[foot]) for foot in ("left", "right"))
+    out = {}
+    for foot in ("left", "right"):
+        cp = np.zeros((B, C, 12))
+        ct = np.zeros((B, C, 2))
+        for c, (act, deact, slot) in enumerate(lists[foot]):
+            yaw = poses[:, slot, 2]
+            cs, sn = np.cos(yaw), np.sin(yaw)
+            cp[:, c, 0] = poses[:, slot, 0]
+            cp[:, c, 1] = poses[:, slot, 1]
+            cp[:, c, 3], cp[:, c, 4] = cs, -sn
+            cp[:, c, 6], cp[:, c, 7] = sn, cs
+            cp[:, c, 11] = 1.0
+            ct[:, c, 0] = act * dt
+            ct[:, c, 1] = deact * dt
+        out[foot] = dict(contact_pose=cp, contact_time=ct,
+                         ncontacts=np.full(B, len(lists[foot]), dtype=np.int32))
+    return out
+
+
 def window(full, start, horizon, xi_init=None):
     """Receding-horizon window [start, start + horizon) of a longer plan (make_batch with a
     horizon of at least start + horizon): the per-knot arrays of knots start.., the references of

@@ -625,6 +625,55 @@ blf_status blf_contact_rls_advance(blf_handle* handle, double lambda, const doub
                               (hipStream_t)stream);
 }
 
+blf_status blf_swing_foot_eval(blf_handle* handle, const blf_swing_foot_params* params,
+                               const double* contact_pose, const double* contact_time,
+                               const int32_t* ncontacts, int64_t batch, const double* tq,
+                               int32_t nq, double* pose, double* twist, double* accel,
+                               int32_t* contact_idx, int32_t* in_contact, void* stream)
+{
+    BLF_REQUIRE(handle != nullptr, "blf_swing_foot_eval: null handle");
+    BLF_REQUIRE(params != nullptr, "blf_swing_foot_eval: null params");
+    BLF_REQUIRE(params->reserved == 0, "blf_swing_foot_eval: params->reserved must be 0");
+    BLF_REQUIRE(std::isfinite(params->step_height) && params->step_height >= 0.0,
+                "blf_swing_foot_eval: step_height=%g, must be finite and >= 0", params->step_height);
+    BLF_REQUIRE(params->apex_ratio > 0.0 && params->apex_ratio < 1.0,
+                "blf_swing_foot_eval: apex_ratio=%g outside (0, 1)", params->apex_ratio);
+    BLF_REQUIRE(std::isfinite(params->landing_velocity),
+                "blf_swing_foot_eval: landing_velocity is not finite");
+    BLF_REQUIRE(std::isfinite(params->landing_acceleration),
+                "blf_swing_foot_eval: landing_acceleration is not finite");
+    BLF_REQUIRE(batch >= 0, "blf_swing_foot_eval: negative batch");
+    BLF_REQUIRE(nq >= 0, "blf_swing_foot_eval: negative nq");
+    BLF_REQUIRE(contact_pose != nullptr, "blf_swing_foot_eval: null contact_pose");
+    BLF_REQUIRE(contact_time != nullptr, "blf_swing_foot_eval: null contact_time");
+    BLF_REQUIRE(ncontacts != nullptr, "blf_swing_foot_eval: null ncontacts");
+    BLF_REQUIRE(tq != nullptr, "blf_swing_foot_eval: null tq");
+    BLF_REQUIRE(pose || twist || accel || contact_idx || in_contact,
+                "blf_swing_foot_eval: no output requested");
+    if (params->max_contacts < 1 || params->max_contacts > BLF_SWING_MAX_CONTACTS)
+        return set_error(BLF_ERR_UNSUPPORTED, "blf_swing_foot_eval: max_contacts=%d outside [1, %d]",
+                         params->max_contacts, BLF_SWING_MAX_CONTACTS);
+    return launch_swing_foot_eval(params, contact_pose, contact_time, ncontacts, batch, tq, nq,
+                                  pose, twist, accel, contact_idx, in_contact,
+                                  (hipStream_t)stream);
+}
+
+blf_status blf_so3_eval(blf_handle* handle, const double* R0, const double* R1,
+                        const double* duration, int64_t batch, const double* tq, int32_t nq,
+                        double* rot, double* omega, double* alpha, void* stream)
+{
+    BLF_REQUIRE(handle != nullptr, "blf_so3_eval: null handle");
+    BLF_REQUIRE(batch >= 0, "blf_so3_eval: negative batch");
+    BLF_REQUIRE(nq >= 0, "blf_so3_eval: negative nq");
+    BLF_REQUIRE(R0 != nullptr, "blf_so3_eval: null R0");
+    BLF_REQUIRE(R1 != nullptr, "blf_so3_eval: null R1");
+    BLF_REQUIRE(duration != nullptr, "blf_so3_eval: null duration");
+    BLF_REQUIRE(tq != nullptr, "blf_so3_eval: null tq");
+    BLF_REQUIRE(rot || omega || alpha, "blf_so3_eval: no output requested");
+    return launch_so3_eval(R0, R1, duration, batch, tq, nq, rot, omega, alpha,
+                           (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 static blf_status check_fbd(const char* fn, blf_handle* handle, const blf_fb_model* model,

@@ -120,6 +120,13 @@ blf_status launch_contact_rls(double lambda, const double* meas_cov, int shared_
                               const double* pose, const double* null_pose, const double* wrench,
                               int32_t steps, double* state, double* cov, int64_t batch,
                               hipStream_t s);
+blf_status launch_swing_foot_eval(const blf_swing_foot_params* p, const double* cpose,
+                                  const double* ctime, const int32_t* ncontacts, int64_t L,
+                                  const double* tq, int32_t Q, double* pose, double* twist,
+                                  double* accel, int32_t* cidx, int32_t* incontact, hipStream_t s);
+blf_status launch_so3_eval(const double* R0, const double* R1, const double* duration, int64_t S,
+                           const double* tq, int32_t Q, double* rot, double* omega, double* alpha,
+                           hipStream_t s);
 blf_status launch_fbk_dynamics(int n, double rho, const double* rot, const double* twist,
                                const double* joint_vel, double* dpos, double* drot,
                                double* djoints, int64_t batch, hipStream_t s);

@@ -18,6 +18,7 @@
 //    t_j <= t, -1 if none; the evaluated segment is that index clamped to [0, K-1].
 // Built with -ffp-contract=off; same expression order as oracle/blf_oracle.c.
 #include "blf_internal.h"
+#include "quintic_math.h"
 #include "slab.h"
 
 namespace blf {
@@ -512,27 +513,13 @@ __global__ __launch_bounds__(256) void quintic_fit_kernel(const double* __restri
     const double* t = kt + sp * K1;
     const double* pva = kp + sp * K1 * 3 * D;
     const double T = t[j + 1] - t[j];
-    const double T2 = T * T;
-    const double T3 = T2 * T;
-    const double T4 = T3 * T;
-    const double T5 = T4 * T;
     const double p0 = pva[(j * 3 + 0) * D + d];
     const double v0 = pva[(j * 3 + 1) * D + d];
     const double a0 = pva[(j * 3 + 2) * D + d];
     const double p1 = pva[((j + 1) * 3 + 0) * D + d];
     const double v1 = pva[((j + 1) * 3 + 1) * D + d];
     const double a1 = pva[((j + 1) * 3 + 2) * D + d];
-    const double c2 = 0.5 * a0;
-    const double h = p1 - ((p0 + v0 * T) + c2 * T2);
-    const double hv = v1 - (v0 + a0 * T);
-    const double ha = a1 - a0;
-    double* c = coeffs + ((sp * K + j) * D + d) * 6;
-    c[0] = p0;
-    c[1] = v0;
-    c[2] = c2;
-    c[3] = ((10.0 * h - 4.0 * (hv * T)) + 0.5 * (ha * T2)) / T3;
-    c[4] = ((-15.0 * h + 7.0 * (hv * T)) - ha * T2) / T4;
-    c[5] = ((6.0 * h - 3.0 * (hv * T)) + 0.5 * (ha * T2)) / T5;
+    quintic_fit_coeffs(T, p0, v0, a0, p1, v1, a1, coeffs + ((sp * K + j) * D + d) * 6);
 }
 
 // one lane per (spline, query); the workgroup's [256][3][D] output slab is staged in LDS and
@@ -611,9 +598,8 @@ __global__ __launch_bounds__(kEvalBlock) void quintic_eval_kernel(const double* 
             } else {
                 c0 = cp[0]; c1 = cp[1]; c2 = cp[2]; c3 = cp[3]; c4 = cp[4]; c5 = cp[5];
             }
-            const double p = c0 + tau * (c1 + tau * (c2 + tau * (c3 + tau * (c4 + tau * c5))));
-            const double v = c1 + tau * (2.0 * c2 + tau * (3.0 * c3 + tau * (4.0 * c4 + tau * (5.0 * c5))));
-            const double a = 2.0 * c2 + tau * (6.0 * c3 + tau * (12.0 * c4 + tau * (20.0 * c5)));
+            double p, v, a;
+            quintic_horner(tau, c0, c1, c2, c3, c4, c5, p, v, a);
             o[d] = p;
             o[D + d] = v;
             o[2 * D + d] = a;

@@ -54,6 +54,9 @@
  *   blf_contact_rls_advance   the same advance() with ContinuousContactModel::getRegressor()
  *                             (ContinuousContactModel.cpp:223-254) as the regressor function: the
  *                             online identification of a contact's spring and damper
+ *   blf_swing_foot_eval / blf_so3_eval  ABSENT in the reference snapshot (SwingFootPlanner and
+ *                             SO3Planner, added upstream later): defined by section 11 below; the
+ *                             contact lookup is getPresentContact (ContactList.cpp:190-202)
  */
 #ifndef BLF_C_H
 #define BLF_C_H
@@ -93,7 +96,9 @@ blf_status blf_destroy(blf_handle* handle);
 const char* blf_last_error(void);
 /* Version string of the library: "blf-mi355x <version> (abi <n>, ...) src <hash>".  ABI 3 (0.3.0)
  * is additive: it adds blf_rls_advance and blf_contact_rls_advance and changes no existing entry
- * point or struct.  ABI 2 (0.2.0) added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
+ * point or struct.  blf_swing_foot_eval and blf_so3_eval were added within ABI 3 (no existing
+ * entry point or struct changed, so the number stays): a caller detects them by symbol
+ * (dlsym).  ABI 2 (0.2.0) added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
  * a caller built against an older header must zero-initialise these structs (`= {0}`), since the
  * library reads every field as a device pointer or NULL.  Solves that use a stream's stage-2 list
  * (blf_dcm_mpc_solve*) are refused with BLF_ERR_UNSUPPORTED while that stream is being captured
@@ -607,6 +612,85 @@ blf_status blf_contact_rls_advance(blf_handle* handle, double lambda, const doub
                                    int32_t shared_geometry, const double* twist, const double* pose,
                                    const double* null_pose, const double* wrench, int32_t steps,
                                    double* state, double* covariance, int64_t batch, void* stream);
+
+/* ---- 11. Swing-foot and SO(3) trajectories (Planners::SwingFootPlanner, SO3Planner), batched ----
+ * Both classes are absent from the reference snapshot (upstream added them later); this section
+ * defines them.  Poses are {p[3], R[9] row-major}; twists and accelerations are mixed: [0..2] the
+ * linear part of the frame origin in the world, [3..5] the angular part in the world.  No FMA
+ * contraction; every sum below is evaluated left to right.
+ *
+ * blf_swing_foot_eval: L contact lists (one foot each) of up to C = params->max_contacts contacts,
+ *   contact_pose [L][C][12], contact_time [L][C][2] = (activation, deactivation), ncontacts [L];
+ *   each list sorted and non-overlapping (as ContactList guarantees); queries tq [L][Q].
+ * Outputs, each optional (NULL: not written): pose [L][Q][12], twist [L][Q][6], accel [L][Q][6],
+ *   contact_idx [L][Q], in_contact [L][Q] (int32).
+ * For one list of n contacts (pose_c, act_c, deact_c) and one query time t:
+ *   raw = the last c < n with act_c <= t, or -1 (the getPresentContact rule, ContactList.cpp:
+ *   190-202); contact_idx = raw.
+ *   raw == -1:                      pose of contact 0, zero twist / accel, in_contact = 0
+ *   t < deact_raw (stance):         pose of contact raw bit for bit, zeros, in_contact = 1
+ *   t >= deact_raw, raw == n - 1:   pose of the last contact, zeros, in_contact = 0
+ *   otherwise: swing from contact raw to raw + 1, in_contact = 0, with t0 = deact_raw,
+ *   t1 = act_{raw+1}, T = t1 - t0, tau = (t - t0) / T.
+ *   A query is poisoned when n is outside [1, C], when t is not finite, or when any pose or time
+ *   value of its list's contacts c < n is not finite: every floating output of the query is NaN,
+ *   contact_idx = -1, in_contact = 0; other queries are unaffected.
+ * Swing translation: the 3-knot quintic spline of section 4 (the expressions of blf_quintic_fit /
+ *   _eval in their order), h = step_height, rho = apex_ratio, p_a = p_raw, p_b = p_{raw+1}:
+ *     lift knot  t0:  position p_a, zero velocity and acceleration
+ *     apex knot  tm = (1 - rho) * t0 + rho * t1:  xy position (1 - rho) * p_a + rho * p_b,
+ *                z position max(z_a, z_b) + h, velocity ((p_b - p_a)_xy / T, 0), zero acceleration
+ *     land knot  t1:  position p_b, velocity (0, 0, landing_velocity), acceleration
+ *                (0, 0, landing_acceleration)
+ *   evaluated on the segment of the last knot <= t (t < tm: the first) at t - (that knot's time).
+ * Swing rotation: minimum jerk on the geodesic, R(t) = Exp(s phi) R_a, omega = sdot phi,
+ *   alpha = sddot phi, phi = Log(R_b R_a^T) = theta u, with
+ *     s = ((tau*tau)*tau) * (10 + tau*(-15 + 6*tau))
+ *     sdot = ((tau*tau) * (30 + tau*(-60 + 30*tau))) / T
+ *     sddot = (tau * (60 + tau*(-180 + 120*tau))) / (T*T)
+ * Log: E = R_b R_a^T, E_ij = (b_i0 a_j0 + b_i1 a_j1) + b_i2 a_j2; tr = (E00 + E11) + E22; the
+ *   (unnormalised) quaternion of E by Shepperd's rule, the branch being the largest of tr, E00, E11,
+ *   E22 (the first of equals, in that order):
+ *     tr:  g = 2 sqrt(1 + tr);                w = g/4, x = (E21-E12)/g, y = (E02-E20)/g, z = (E10-E01)/g
+ *     E00: g = 2 sqrt(((1 + E00) - E11) - E22); w = (E21-E12)/g, x = g/4, y = (E01+E10)/g, z = (E02+E20)/g
+ *     E11: g = 2 sqrt(((1 + E11) - E00) - E22); w = (E02-E20)/g, x = (E01+E10)/g, y = g/4, z = (E12+E21)/g
+ *     E22: g = 2 sqrt(((1 + E22) - E00) - E11); w = (E10-E01)/g, x = (E02+E20)/g, y = (E12+E21)/g, z = g/4
+ *   negated when w < 0; nv = sqrt((x*x + y*y) + z*z), theta = 2 atan2(nv, w), u = (x, y, z) / nv.
+ *   nv == 0 is the only special case: phi = 0 and R(t) is R_a copied bit for bit.  There is no
+ *   small-angle threshold (the quaternion route is well conditioned from 0 up to pi).  At exactly
+ *   pi (w == 0) the sign of u, hence the side the rotation turns through, is whichever the branch
+ *   gives: the end points are the same, the path between them is one of two.
+ * Exp: a = s * theta, sa = sin(a), sh = sin(0.5 * a), cv = 2 * (sh * sh);
+ *   M_ii = 1 + cv * (u_i*u_i - 1);  M_ij = sa * K_ij + cv * (u_i*u_j) for i != j, with
+ *   K = [u]x (K01 = -u2, K02 = u1, K10 = u2, K12 = -u0, K20 = -u1, K21 = u0);
+ *   R_ij = (M_i0 a_0j + M_i1 a_1j) + M_i2 a_2j;  omega_i = sdot * (theta * u_i), alpha likewise.
+ * Errors: null handle, params, input pointer or no output at all, negative batch / nq, reserved
+ * != 0, step_height negative or not finite, apex_ratio outside (0, 1), a landing term not finite:
+ * BLF_ERR_INVALID_ARGUMENT; max_contacts outside [1, BLF_SWING_MAX_CONTACTS]: BLF_ERR_UNSUPPORTED;
+ * batch == 0 or nq == 0: BLF_OK. */
+#define BLF_SWING_MAX_CONTACTS 16
+typedef struct blf_swing_foot_params {
+    int32_t max_contacts;         /* C, 1..BLF_SWING_MAX_CONTACTS (padded contacts per list)   */
+    int32_t reserved;             /* must be 0                                                 */
+    double step_height;           /* h >= 0 above the higher of the two contacts [m]           */
+    double apex_ratio;            /* rho in (0, 1): the apex time as a fraction of the swing   */
+    double landing_velocity;      /* vertical velocity at touch-down [m/s]                     */
+    double landing_acceleration;  /* vertical acceleration at touch-down [m/s^2]               */
+} blf_swing_foot_params;
+blf_status blf_swing_foot_eval(blf_handle* handle, const blf_swing_foot_params* params,
+                               const double* contact_pose, const double* contact_time,
+                               const int32_t* ncontacts, int64_t batch, const double* tq,
+                               int32_t nq, double* pose, double* twist, double* accel,
+                               int32_t* contact_idx, int32_t* in_contact, void* stream);
+
+/* blf_so3_eval: S minimum-jerk rotation trajectories from R0 [S][9] to R1 [S][9] over duration [S],
+ * queried at tq [S][Q], clamped to [0, duration]: tau = clamp(t) / duration, T = duration, R_a = R0,
+ * R_b = R1 in the rotation rule above.  Outputs, each optional: rot [S][Q][9], omega [S][Q][3],
+ * alpha [S][Q][3].  A duration that is not finite and positive, or a non-finite t, R0 or R1 value,
+ * gives NaN in that query's outputs.  Errors as blf_swing_foot_eval. */
+blf_status blf_so3_eval(blf_handle* handle, const double* R0, const double* R1,
+                        const double* duration, int64_t batch, const double* tq, int32_t nq,
+                        double* rot, double* omega, double* alpha, void* stream);
 
 /* Algorithmic flop count of one IPM iteration of one problem (what the fp64 roofline field
  * of bench.py is computed from); `active_facets` = sum_k nfacets[k]. */
