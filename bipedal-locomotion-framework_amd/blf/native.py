@@ -30,7 +30,7 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_fbk_euler_integrate", "blf_fbd_dynamics", "blf_fbd_euler_integrate",
             "blf_fb_dcm", "blf_dcm_posture_reference", "blf_fbd_euler_integrate_impedance",
             "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance",
-            "blf_swing_foot_eval", "blf_so3_eval"]
+            "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -79,6 +79,16 @@ class SwingFootParams(ctypes.Structure):
     _fields_ = [("max_contacts", _i32), ("reserved", _i32), ("step_height", _f64),
                 ("apex_ratio", _f64), ("landing_velocity", _f64), ("landing_acceleration", _f64)]
 
+
+class IkTasks(ctypes.Structure):
+    """blf_ik_tasks (include/blf/blf_c.h section 12); every pointer is device memory."""
+    _fields_ = [("nse3", _i32), ("reserved", _i32), ("frame", _vp), ("se3_weight", _vp), ("se3_kp", _vp),
+                ("se3_pose", _vp), ("se3_twist", _vp), ("com_weight", _vp), ("com_kp", _f64),
+                ("com_pos", _vp), ("com_vel", _vp), ("joint_weight", _vp), ("joint_kp", _vp),
+                ("joint_pos", _vp), ("joint_vel", _vp), ("base_damping", _f64)]
+
+
+IK_OK, IK_NOT_POSITIVE, IK_BAD_INPUT = 0, 1, 2   # per-robot status of fb_ik_solve / fb_ik_integrate
 
 SWING_OUTPUTS = ("pose", "twist", "accel", "contact_idx", "in_contact")
 SO3_OUTPUTS = ("rot", "omega", "alpha")
@@ -214,6 +224,10 @@ def lib():
         L.blf_swing_foot_eval.argtypes = [_vp, ctypes.POINTER(SwingFootParams), _vp, _vp, _vp, _i64,
                                           _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
         L.blf_so3_eval.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]
+        L.blf_fb_ik_solve.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
+                                      ctypes.POINTER(IkTasks), _i64, _vp, _vp, _vp]
+        L.blf_fb_ik_integrate.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
+                                          ctypes.POINTER(IkTasks), _i64, _i32, _f64, _vp, _vp, _vp]
         L.blf_dcm_mpc_flops_per_iter.restype = _f64
         L.blf_set_qp_launch_mode.argtypes = [_i32, _i32]
         for name in EXPORTED:
@@ -970,6 +984,81 @@ class Handle:
                                         _ptr(twist, torch.float64, (B, K, 6), "twist"),
                                         _stream(stream)))
         return pose, twist
+
+    # ---- whole-body inverse kinematics (include/blf/blf_c.h section 12) ------------------------
+    def ik_tasks(self, batch, ndof, frame=None, se3_weight=None, se3_kp=None, se3_pose=None, se3_twist=None,
+                 com_weight=None, com_kp=0.0, com_pos=None, com_vel=None, joint_weight=None,
+                 joint_kp=None, joint_pos=None, joint_vel=None, base_damping=0.0):
+        """Build a blf_ik_tasks for `batch` robots of `ndof` joints (e.g. **robot.standing_ik_tasks):
+        frame [K] int32, se3_weight [K,6], se3_kp [K,2], se3_pose [B,K,12], se3_twist [B,K,6] or
+        None, com_weight [3] or None (no CoM task), com_pos / com_vel [B,3], joint_weight / joint_kp
+        [n], joint_pos / joint_vel [B,n].  Host arrays are uploaded; device tensors are used as they
+        are (so a blf_swing_foot_eval pose output feeds se3_pose without a copy).  Returns an object
+        with the struct (.c) and the tensors (.t) it keeps alive."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+
+        class _T:
+            pass
+        tk = _T()
+        B, n = int(batch), int(ndof)
+        K = 0 if frame is None else int(len(frame))
+
+        def up(a, dtype):
+            if isinstance(a, torch.Tensor):
+                return a
+            return torch.as_tensor(a, dtype=dtype).contiguous().to(dev)
+        spec = dict(frame=(frame, torch.int32, (K,)), se3_weight=(se3_weight, torch.float64, (K, 6)),
+                    se3_kp=(se3_kp, torch.float64, (K, 2)), se3_pose=(se3_pose, torch.float64, (B, K, 12)),
+                    se3_twist=(se3_twist, torch.float64, (B, K, 6)), com_weight=(com_weight, torch.float64, (3,)),
+                    com_pos=(com_pos, torch.float64, (B, 3)), com_vel=(com_vel, torch.float64, (B, 3)),
+                    joint_weight=(joint_weight, torch.float64, (n,)), joint_kp=(joint_kp, torch.float64, (n,)),
+                    joint_pos=(joint_pos, torch.float64, (B, n)), joint_vel=(joint_vel, torch.float64, (B, n)))
+        c = IkTasks()
+        c.nse3, c.reserved = K, 0
+        c.com_kp, c.base_damping = float(com_kp), float(base_damping)
+        tk.t = {}
+        for k, (a, dt, shape) in spec.items():
+            if a is None or (K == 0 and k in ("frame", "se3_weight", "se3_kp", "se3_pose", "se3_twist")):
+                continue
+            tk.t[k] = up(a, dt)
+            setattr(c, k, _ptr(tk.t[k], dt, shape, k))
+        tk.c, tk.batch, tk.n = c, B, n
+        return tk
+
+    def fb_ik_solve(self, dm, state, tasks, nu=None, status=None, stream=None):
+        """blf_fb_ik_solve: nu [B,6+n] = (base mixed twist, joint velocities) minimising the weighted
+        task errors at the state's base_pos / base_rot / joint_pos, and the per-robot status [B]
+        int32 (IK_OK / IK_NOT_POSITIVE / IK_BAD_INPUT; status=False: not requested)."""
+        torch = _torch()
+        B, n = state["joint_pos"].shape
+        dev = state["joint_pos"].device
+        nu = nu if nu is not None else torch.empty((B, 6 + n), dtype=torch.float64, device=dev)
+        if status is None:
+            status = torch.empty((B,), dtype=torch.int32, device=dev)
+        sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
+        _check(lib().blf_fb_ik_solve(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
+                                     ctypes.byref(tasks.c), B, _ptr(nu, torch.float64, (B, 6 + n), "nu"), sp,
+                                     _stream(stream)))
+        return nu, (status if status is not False else None)
+
+    def fb_ik_integrate(self, dm, state, tasks, steps, dT, nu=None, status=None, stream=None):
+        """blf_fb_ik_integrate: `steps` x (solve, one Euler step of dT) in one launch, in place on
+        `state` (base_vel / joint_vel receive the last step's nu).  nu / status as fb_ik_solve;
+        False: not requested.  Returns (state, nu, status)."""
+        torch = _torch()
+        B, n = state["joint_pos"].shape
+        dev = state["joint_pos"].device
+        if nu is None:
+            nu = torch.empty((B, 6 + n), dtype=torch.float64, device=dev)
+        if status is None:
+            status = torch.empty((B,), dtype=torch.int32, device=dev)
+        np_ = _ptr(nu, torch.float64, (B, 6 + n), "nu") if nu is not False else None
+        sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
+        _check(lib().blf_fb_ik_integrate(self._h, ctypes.byref(dm.c),
+                                         ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c), B,
+                                         int(steps), float(dT), np_, sp, _stream(stream)))
+        return state, (nu if nu is not False else None), (status if status is not False else None)
 
     # ---- config 5: the closed loop's maps (DESIGN.md section 11) ----------------------------------
     def fb_dcm(self, dm, state, omega=None, column=0, com=None, xi=None, stream=None):

@@ -254,6 +254,40 @@ def sole_null_poses(model, states):
     return null
 
 
+def nominal_com_offset(model):
+    """The centre of mass relative to the base origin at the nominal posture (all joints 0, base
+    orientation identity)."""
+    n = model["n"]
+    Rl = [np.eye(3)] + [None] * n
+    pl = [np.zeros(3)] + [None] * n
+    for j in range(n):
+        P = model["parent"][j]
+        Rl[j + 1] = Rl[P] @ model["joint_rot"][j]
+        pl[j + 1] = pl[P] + Rl[P] @ model["joint_origin"][j]
+    m = np.asarray(model["link_mass"], dtype=np.float64)
+    c = np.array([pl[l] + Rl[l] @ model["link_com"][l] for l in range(n + 1)])
+    return (m[:, None] * c).sum(axis=0) / m.sum()
+
+
+def standing_ik_tasks(model, states, se3_weight=10.0, com_weight=10.0, joint_weight=0.1, kp_linear=5.0,
+                      kp_angular=5.0, com_kp=5.0, joint_kp=1.0, base_damping=1.0e-3):
+    """The standing task set of the whole-body IK (blf_ik_tasks fields as host arrays, for
+    native.Handle.ik_tasks): an SE3 task per sole frame holding it flat on the ground under the base
+    (sole_null_poses), the CoM over the middle of the soles at its nominal height, and a posture
+    regularisation towards the nominal joint positions."""
+    B, n = states["joint_pos"].shape
+    F = len(model["frame_link"])
+    pose = sole_null_poses(model, states)
+    com_pos = pose[:, :, :3].mean(axis=1)
+    com_pos[:, 2] = nominal_com_offset(model)[2] - sole_offsets(model)[:, 2].mean()
+    return dict(frame=np.arange(F, dtype=np.int32), se3_weight=np.full((F, 6), float(se3_weight)),
+                se3_kp=np.tile([float(kp_linear), float(kp_angular)], (F, 1)), se3_pose=pose,
+                se3_twist=None, com_weight=np.full(3, float(com_weight)), com_kp=float(com_kp),
+                com_pos=com_pos, com_vel=None, joint_weight=np.full(n, float(joint_weight)),
+                joint_kp=np.full(n, float(joint_kp)), joint_pos=np.zeros((B, n)), joint_vel=None,
+                base_damping=float(base_damping))
+
+
 def joint_inertias(model):
     """Composite inertia of every joint's subtree about the joint axis at the nominal posture
     (joints 0, base identity): sum over the subtree's links of z^T R I_c R^T z + m |z x (c - o)|^2."""

@@ -822,3 +822,98 @@ blf_status blf_fbd_euler_integrate(blf_handle* handle, const blf_fb_model* model
 }
 
 }  // extern "C"
+
+// The checks blf_fb_ik_solve and blf_fb_ik_integrate share.  The shared weight and gain arrays are
+// device memory: they are copied to the host on the call's stream and checked there before the
+// launch (section 12: a staged copy).
+static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_model* model,
+                           const blf_fb_state* state, const blf_ik_tasks* t, int64_t batch,
+                           hipStream_t s)
+{
+    BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
+    BLF_REQUIRE(model != nullptr && state != nullptr, "%s: null model / state", fn);
+    BLF_REQUIRE(t != nullptr, "%s: null tasks", fn);
+    BLF_REQUIRE(t->reserved == 0, "%s: tasks->reserved must be 0", fn);
+    BLF_REQUIRE(batch >= 0, "%s: negative batch", fn);
+    if (model->ndof < 1 || model->ndof > BLF_FBD_MAX_DOFS)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: ndof=%d outside [1, %d]", fn, model->ndof,
+                         BLF_FBD_MAX_DOFS);
+    if (t->nse3 < 0 || t->nse3 > BLF_IK_MAX_SE3_TASKS)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: nse3=%d outside [0, %d]", fn, t->nse3,
+                         BLF_IK_MAX_SE3_TASKS);
+    const int n = model->ndof, K = t->nse3;
+    BLF_REQUIRE(model->parent && model->joint_origin && model->joint_rot && model->joint_axis &&
+                    model->link_mass && model->link_com && model->link_inertia,
+                "%s: null model array", fn);
+    BLF_REQUIRE(K == 0 || (t->frame && t->se3_weight && t->se3_kp && model->frame_link &&
+                           model->frame_pose && model->nframes > 0),
+                "%s: null SE3 task array", fn);
+    BLF_REQUIRE(t->joint_weight && t->joint_kp, "%s: null joint task array", fn);
+    BLF_REQUIRE(std::isfinite(t->base_damping) && t->base_damping >= 0.0,
+                "%s: base_damping=%g, must be finite and >= 0", fn, t->base_damping);
+    BLF_REQUIRE(t->com_weight == nullptr || (std::isfinite(t->com_kp) && t->com_kp >= 0.0),
+                "%s: com_kp=%g, must be finite and >= 0", fn, t->com_kp);
+    if (batch == 0) return BLF_OK;
+    BLF_REQUIRE(state->base_pos && state->base_rot && state->joint_pos, "%s: null state buffer", fn);
+    BLF_REQUIRE(K == 0 || t->se3_pose, "%s: null se3_pose", fn);
+    BLF_REQUIRE(t->com_weight == nullptr || t->com_pos, "%s: com_weight given without com_pos", fn);
+    BLF_REQUIRE(t->joint_pos != nullptr, "%s: null joint_pos set point", fn);
+    // the staged copy: se3_weight 6K | se3_kp 2K | com_weight 3 | joint_weight n | joint_kp n
+    double hbuf[8 * BLF_IK_MAX_SE3_TASKS + 3 + 2 * BLF_FBD_MAX_DOFS];
+    const bool com = t->com_weight != nullptr;
+    const struct { const double* src; int count; } parts[5] = {
+        {t->se3_weight, 6 * K}, {t->se3_kp, 2 * K}, {t->com_weight, com ? 3 : 0},
+        {t->joint_weight, n}, {t->joint_kp, n}};
+    int at = 0;
+    for (const auto& p : parts) {
+        if (p.count > 0) {
+            const blf_status st = check_hip(
+                hipMemcpyAsync(hbuf + at, p.src, sizeof(double) * p.count, hipMemcpyDeviceToHost, s),
+                "blf_fb_ik: staging the task weights");
+            if (st != BLF_OK) return st;
+        }
+        at += p.count;
+    }
+    const blf_status st = check_hip(hipStreamSynchronize(s), "blf_fb_ik: staging the task weights");
+    if (st != BLF_OK) return st;
+    const int jw0 = 8 * K + (com ? 3 : 0);
+    for (int i = 0; i < at; ++i) {
+        const double v = hbuf[i];
+        const bool positive = i >= jw0 && i < jw0 + n;   // joint_weight
+        BLF_REQUIRE(std::isfinite(v) && (positive ? v > 0.0 : v >= 0.0),
+                    "%s: %s[%d]=%g, must be finite and %s", fn,
+                    i < 6 * K ? "se3_weight" : i < 8 * K ? "se3_kp" : i < jw0 ? "com_weight"
+                    : positive ? "joint_weight" : "joint_kp",
+                    i < 6 * K ? i : i < 8 * K ? i - 6 * K : i < jw0 ? i - 8 * K : positive ? i - jw0 : i - jw0 - n,
+                    v, positive ? "> 0" : ">= 0");
+    }
+    if (fb_ik_lds_bytes(n, K) > 160 * 1024)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    return BLF_OK;
+}
+
+extern "C" {
+
+blf_status blf_fb_ik_solve(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                           const blf_ik_tasks* tasks, int64_t batch, double* nu, int32_t* status,
+                           void* stream)
+{
+    const blf_status st = check_ik("blf_fb_ik_solve", handle, model, state, tasks, batch, (hipStream_t)stream);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch == 0 || nu != nullptr, "blf_fb_ik_solve: null nu");
+    return launch_fb_ik(model, state, tasks, batch, 0, 0.0, nu, status, (hipStream_t)stream);
+}
+
+blf_status blf_fb_ik_integrate(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                               const blf_ik_tasks* tasks, int64_t batch, int32_t steps, double dT,
+                               double* nu, int32_t* status, void* stream)
+{
+    BLF_REQUIRE(steps >= 1, "blf_fb_ik_integrate: steps=%d, must be >= 1", steps);
+    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_fb_ik_integrate: dT=%g, must be finite and positive", dT);
+    const blf_status st = check_ik("blf_fb_ik_integrate", handle, model, state, tasks, batch, (hipStream_t)stream);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel), "blf_fb_ik_integrate: null state buffer");
+    return launch_fb_ik(model, state, tasks, batch, steps, dT, nu, status, (hipStream_t)stream);
+}
+
+}  // extern "C"

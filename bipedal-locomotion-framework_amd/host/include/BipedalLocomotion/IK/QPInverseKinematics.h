@@ -1,0 +1,119 @@
+/**
+ * @file QPInverseKinematics.h
+ * Upstream's IK::QPInverseKinematics over SE3Task, CoMTask and JointTrackingTask, for one robot:
+ * advance() solves for the generalized velocity nu = (base mixed twist, joint velocities) that
+ * minimises the weighted task errors at the robot state, on the device (blf_fb_ik_solve,
+ * include/blf/blf_c.h section 12).  Integrating that velocity with
+ * ForwardEuler<FloatingBaseSystemKinematics> and feeding the state back with setRobotState() is
+ * upstream's IntegrationBasedIK loop; blf_fb_ik_integrate runs the same loop in one launch.
+ *
+ * Differences from upstream a user can notice: only weighted (priority 1) tasks: addTask() with
+ * priority 0 returns false; at most BLF_IK_MAX_SE3_TASKS SE3 tasks, one CoM task and one joint
+ * tracking task, which is required (it makes the problem positive definite); the robot is a
+ * blf::RobotModel set with setRobotModel() (no iDynTree KinDynComputations) and its state is given
+ * with setRobotState(); set points and the state hold blf::Transform / blf::Vector6 (no manif
+ * types); the optional key "base_damping" (default 0) is added to the base diagonal.
+ */
+#ifndef BLF_BIPEDAL_LOCOMOTION_IK_QP_INVERSE_KINEMATICS_H
+#define BLF_BIPEDAL_LOCOMOTION_IK_QP_INVERSE_KINEMATICS_H
+
+#include <memory>
+#include <string>
+#include <vector>
+
+#include <BipedalLocomotion/IK/CoMTask.h>
+#include <BipedalLocomotion/IK/IKLinearTask.h>
+#include <BipedalLocomotion/IK/JointTrackingTask.h>
+#include <BipedalLocomotion/IK/SE3Task.h>
+#include <BipedalLocomotion/System/Advanceable.h>
+#include <BipedalLocomotion/System/FloatingBaseSystemDynamics.h>   // blf::RobotModel
+#include <blf/dense.h>
+#include <blf/device.h>
+#include <blf/spatial.h>
+
+namespace BipedalLocomotion
+{
+namespace IK
+{
+
+struct IntegrationBasedIKState
+{
+    blf::VectorXd jointVelocity;
+    blf::Vector6 baseVelocity{};   /**< (linear, angular), mixed representation */
+};
+
+class QPInverseKinematics : public System::Advanceable<IntegrationBasedIKState>
+{
+public:
+    /** Optional key "base_damping" (finite, >= 0; default 0).  False if the handler is expired or
+     * the value is out of range. */
+    bool initialize(std::weak_ptr<ParametersHandler::IParametersHandler> handler);
+
+    /** The robot (replaces upstream's KinDynComputations) and, optionally, the names of its frames
+     * (frameNames[i] names model.frameLink[i]; what SE3Task's "frame_name" is resolved through).
+     * Fixed joints are merged as FloatingBaseDynamicalSystem::setRobotModel does.  Needs a device. */
+    bool setRobotModel(const blf::RobotModel& model, const std::vector<std::string>& frameNames = {});
+
+    /** The state the next advance() solves at. */
+    bool setRobotState(const blf::Vector3& basePosition, const blf::Matrix3& baseRotation,
+                       const blf::VectorXd& jointPositions);
+
+    /**
+     * Add a task.  priority must be 1 (weighted); weight holds one entry per task row (SE3: 6,
+     * linear xyz then angular xyz; CoM: 3; joint tracking: one per joint, > 0), each finite and
+     * >= 0.  False with a "[QPInverseKinematics::addTask] ..." line for priority 0 (or any other
+     * value), a null task, a duplicate name, a wrong weight, a fifth SE3 task, a second CoM or
+     * joint tracking task, or after finalize().
+     */
+    bool addTask(std::shared_ptr<IKLinearTask> task, const std::string& taskName, unsigned int priority,
+                 const blf::VectorXd& weight = blf::VectorXd());
+
+    std::vector<std::string> getTaskNames() const;
+
+    /** Resolve the frames and fix the task set; false without a model or with an unknown frame. */
+    bool finalize();
+
+    /** Solve at the robot state with the tasks' current set points.  False before finalize() or
+     * setRobotState(), without a joint tracking task, when a task has no set point or a wrong size,
+     * or when the device reports a failed solve (the state is then invalid). */
+    bool advance() final;
+    const IntegrationBasedIKState& get() const final { return m_state; }
+    bool isValid() const final { return m_isValid; }
+
+    /** The device-side description of the last advance() (for callers that go on with
+     * blf_fb_ik_integrate): valid until the next advance(). */
+    const blf_fb_model& deviceModel() const { return m_cModel; }
+    const blf_fb_state& deviceState() const { return m_cState; }
+    const blf_ik_tasks& deviceTasks() const { return m_cTasks; }
+
+private:
+    struct Entry
+    {
+        std::string name;
+        std::shared_ptr<IKLinearTask> task;
+        std::vector<double> weight;
+    };
+    std::vector<Entry> m_tasks;
+    std::vector<int32_t> m_frames;
+    int m_comTask{-1}, m_jointTask{-1};
+    bool m_isFinalized{false}, m_hasModel{false}, m_hasState{false}, m_isValid{false};
+    double m_baseDamping{0.0};
+    blf::RobotModel m_model;
+    std::vector<std::string> m_frameNames;
+    blf::Vector3 m_basePosition{};
+    blf::Matrix3 m_baseRotation{};
+    blf::VectorXd m_jointPositions;
+    IntegrationBasedIKState m_state;
+
+    blf::DeviceBuffer<int32_t> m_dParent, m_dFrameLink, m_dJointType, m_dInt;
+    blf::DeviceBuffer<double> m_dOrigin, m_dRot, m_dAxis, m_dMass, m_dCom, m_dInertia, m_dFramePose;
+    blf::DeviceBuffer<double> m_dData;
+    blf_fb_model m_cModel{};
+    blf_fb_state m_cState{};
+    blf_ik_tasks m_cTasks{};
+};
+
+} // namespace IK
+} // namespace BipedalLocomotion
+
+#endif // BLF_BIPEDAL_LOCOMOTION_IK_QP_INVERSE_KINEMATICS_H

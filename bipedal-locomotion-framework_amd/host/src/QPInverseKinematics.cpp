@@ -1,0 +1,369 @@
+/**
+ * @file QPInverseKinematics.cpp
+ * The task bookkeeping of IK::QPInverseKinematics on the host; every advance() is one
+ * blf_fb_ik_solve for one robot (include/blf/blf_c.h section 12).
+ */
+#include <algorithm>
+#include <cmath>
+#include <iostream>
+
+#include <BipedalLocomotion/IK/QPInverseKinematics.h>
+
+using namespace BipedalLocomotion::IK;
+using namespace BipedalLocomotion::ParametersHandler;
+
+bool QPInverseKinematics::initialize(std::weak_ptr<IParametersHandler> handlerWeak)
+{
+    auto handler = handlerWeak.lock();
+    if (handler == nullptr)
+    {
+        std::cerr << "[QPInverseKinematics::initialize] The parameters handler no longer exists."
+                  << std::endl;
+        return false;
+    }
+    double damping = 0.0;
+    if (handler->getParameter("base_damping", damping) && (!std::isfinite(damping) || damping < 0.0))
+    {
+        std::cerr << "[QPInverseKinematics::initialize] The base_damping must be a non-negative number."
+                  << std::endl;
+        return false;
+    }
+    m_baseDamping = damping;
+    return true;
+}
+
+bool QPInverseKinematics::setRobotModel(const blf::RobotModel& fullModel,
+                                        const std::vector<std::string>& frameNames)
+{
+    constexpr const char* where = "[QPInverseKinematics::setRobotModel] ";
+    m_hasModel = false;
+    m_isValid = false;
+    if (m_isFinalized)
+    {
+        std::cerr << where << "The problem is already finalized." << std::endl;
+        return false;
+    }
+    if (!fullModel.fixedJoint.empty() && !blf::fixedJointMergeable(fullModel))
+    {
+        std::cerr << where << "Corrupted robot model." << std::endl;
+        return false;
+    }
+    const blf::RobotModel model = fullModel.fixedJoint.empty() ? fullModel : blf::reduceFixedJoints(fullModel);
+    const std::size_t n = static_cast<std::size_t>(model.ndof < 0 ? 0 : model.ndof);
+    const std::size_t F = model.frameLink.size();
+    if (model.ndof < 1 || model.ndof > BLF_FBD_MAX_DOFS || model.parent.size() != n
+        || model.jointOrigin.size() != 3 * n || model.jointRotation.size() != 9 * n
+        || model.jointAxis.size() != 3 * n || model.linkMass.size() != n + 1
+        || model.linkCom.size() != 3 * (n + 1) || model.linkInertia.size() != 9 * (n + 1)
+        || model.framePose.size() != 12 * F || (!model.jointType.empty() && model.jointType.size() != n)
+        || (!frameNames.empty() && frameNames.size() != F))
+    {
+        std::cerr << where << "Corrupted robot model." << std::endl;
+        return false;
+    }
+    for (std::size_t j = 0; j < n; ++j)
+        if (model.parent[j] < 0 || model.parent[j] > static_cast<int32_t>(j))
+        {
+            std::cerr << where << "The joints must be in topological order (parent[j] <= j)." << std::endl;
+            return false;
+        }
+    for (const int32_t l : model.frameLink)
+        if (l < 0 || l > model.ndof)
+        {
+            std::cerr << where << "A frame is attached to an unknown link." << std::endl;
+            return false;
+        }
+    for (const int32_t t : model.jointType)
+        if (t != BLF_JOINT_REVOLUTE && t != BLF_JOINT_PRISMATIC)
+        {
+            std::cerr << where << "Unknown joint type " << t << "." << std::endl;
+            return false;
+        }
+    if (blf::threadHandle() == nullptr)
+    {
+        std::cerr << where << "No device." << std::endl;
+        return false;
+    }
+    m_model = model;
+    m_frameNames = frameNames;
+    m_hasModel = m_dParent.upload(model.parent) && m_dOrigin.upload(model.jointOrigin)
+                 && m_dRot.upload(model.jointRotation) && m_dAxis.upload(model.jointAxis)
+                 && m_dMass.upload(model.linkMass) && m_dCom.upload(model.linkCom)
+                 && m_dInertia.upload(model.linkInertia) && m_dFrameLink.upload(model.frameLink)
+                 && m_dFramePose.upload(model.framePose)
+                 && (model.jointType.empty() || m_dJointType.upload(model.jointType));
+    return m_hasModel;
+}
+
+bool QPInverseKinematics::setRobotState(const blf::Vector3& basePosition, const blf::Matrix3& baseRotation,
+                                        const blf::VectorXd& jointPositions)
+{
+    if (!m_hasModel)
+    {
+        std::cerr << "[QPInverseKinematics::setRobotState] Please call 'setRobotModel()' before."
+                  << std::endl;
+        return false;
+    }
+    if (jointPositions.size() != static_cast<std::size_t>(m_model.ndof))
+    {
+        std::cerr << "[QPInverseKinematics::setRobotState] Wrong size of the vectors." << std::endl;
+        return false;
+    }
+    m_basePosition = basePosition;
+    m_baseRotation = baseRotation;
+    m_jointPositions = jointPositions;
+    m_hasState = true;
+    return true;
+}
+
+bool QPInverseKinematics::addTask(std::shared_ptr<IKLinearTask> task, const std::string& taskName,
+                                  unsigned int priority, const blf::VectorXd& weight)
+{
+    constexpr const char* where = "[QPInverseKinematics::addTask] ";
+    if (m_isFinalized)
+    {
+        std::cerr << where << "The problem is already finalized: no task can be added." << std::endl;
+        return false;
+    }
+    if (task == nullptr)
+    {
+        std::cerr << where << "The task " << taskName << " is not valid (null pointer)." << std::endl;
+        return false;
+    }
+    if (priority != 1)
+    {
+        std::cerr << where << "The task " << taskName << " has priority " << priority
+                  << ": only weighted tasks (priority 1) are supported; hard constraints (priority 0) "
+                     "are not."
+                  << std::endl;
+        return false;
+    }
+    for (const Entry& e : m_tasks)
+        if (e.name == taskName)
+        {
+            std::cerr << where << "The task named " << taskName << " already exists." << std::endl;
+            return false;
+        }
+    const IKLinearTask::Kind kind = task->kind();
+    std::size_t se3 = 0;
+    for (const Entry& e : m_tasks) se3 += e.task->kind() == IKLinearTask::Kind::SE3;
+    if (kind == IKLinearTask::Kind::SE3 && se3 >= BLF_IK_MAX_SE3_TASKS)
+    {
+        std::cerr << where << "At most " << BLF_IK_MAX_SE3_TASKS << " SE3 tasks are supported." << std::endl;
+        return false;
+    }
+    if (kind == IKLinearTask::Kind::CoM && m_comTask >= 0)
+    {
+        std::cerr << where << "A CoM task already exists." << std::endl;
+        return false;
+    }
+    if (kind == IKLinearTask::Kind::JointTracking && m_jointTask >= 0)
+    {
+        std::cerr << where << "A joint tracking task already exists." << std::endl;
+        return false;
+    }
+    const bool joint = kind == IKLinearTask::Kind::JointTracking;
+    const std::size_t rows = kind == IKLinearTask::Kind::SE3 ? 6 : kind == IKLinearTask::Kind::CoM ? 3 : weight.size();
+    if (weight.size() != rows || rows == 0)
+    {
+        std::cerr << where << "The weight of the task " << taskName << " has " << weight.size()
+                  << " entries; one per task row is required." << std::endl;
+        return false;
+    }
+    for (std::size_t i = 0; i < rows; ++i)
+        if (!std::isfinite(weight[i]) || weight[i] < 0.0 || (joint && weight[i] == 0.0))
+        {
+            std::cerr << where << "The weight of the task " << taskName << " must be finite and "
+                      << (joint ? "positive." : "non-negative.") << std::endl;
+            return false;
+        }
+    if (kind == IKLinearTask::Kind::CoM) m_comTask = static_cast<int>(m_tasks.size());
+    if (joint) m_jointTask = static_cast<int>(m_tasks.size());
+    m_tasks.push_back(Entry{taskName, std::move(task), std::vector<double>(weight.data(), weight.data() + rows)});
+    return true;
+}
+
+std::vector<std::string> QPInverseKinematics::getTaskNames() const
+{
+    std::vector<std::string> names;
+    for (const Entry& e : m_tasks) names.push_back(e.name);
+    return names;
+}
+
+bool QPInverseKinematics::finalize()
+{
+    constexpr const char* where = "[QPInverseKinematics::finalize] ";
+    if (!m_hasModel)
+    {
+        std::cerr << where << "Please call 'setRobotModel()' before." << std::endl;
+        return false;
+    }
+    std::vector<int32_t> frames;
+    for (const Entry& e : m_tasks)
+    {
+        if (e.task->kind() != IKLinearTask::Kind::SE3) continue;
+        const auto& se3 = static_cast<const SE3Task&>(*e.task);
+        int index = se3.frameIndex();
+        if (!se3.frameName().empty())
+        {
+            const auto it = std::find(m_frameNames.begin(), m_frameNames.end(), se3.frameName());
+            index = it == m_frameNames.end() ? -1 : static_cast<int>(it - m_frameNames.begin());
+        }
+        if (index < 0 || index >= static_cast<int>(m_model.frameLink.size()))
+        {
+            std::cerr << where << "The frame of the task " << e.name << " does not exist in the model."
+                      << std::endl;
+            return false;
+        }
+        frames.push_back(index);
+    }
+    if (m_jointTask >= 0 && m_tasks[m_jointTask].weight.size() != static_cast<std::size_t>(m_model.ndof))
+    {
+        std::cerr << where << "The joint tracking task's weight must have one entry per joint." << std::endl;
+        return false;
+    }
+    m_frames = frames;
+    m_isFinalized = true;
+    return true;
+}
+
+// device data layout (doubles): nu NV | state (bv 6 | jv n | bp 3 | bR 9 | jp n) | se3_weight 6K |
+// se3_kp 2K | se3_pose 12K | se3_twist 6K | com_weight 3 | com_pos 3 | com_vel 3 | joint_weight n |
+// joint_kp n | joint_pos n | joint_vel n; ints: frame K | status 1
+bool QPInverseKinematics::advance()
+{
+    constexpr const char* where = "[QPInverseKinematics::advance] ";
+    m_isValid = false;
+    if (m_jointTask < 0)
+    {
+        std::cerr << where << "A joint tracking task is required: without it the problem is not "
+                              "positive definite."
+                  << std::endl;
+        return false;
+    }
+    if (!m_isFinalized)
+    {
+        std::cerr << where << "Please call 'finalize()' before." << std::endl;
+        return false;
+    }
+    if (!m_hasState)
+    {
+        std::cerr << where << "Please call 'setRobotState()' before." << std::endl;
+        return false;
+    }
+    for (const Entry& e : m_tasks)
+        if (!e.task->isValid())
+        {
+            std::cerr << where << "The task " << e.name << " is not initialized or has no set point."
+                      << std::endl;
+            return false;
+        }
+    const std::size_t n = static_cast<std::size_t>(m_model.ndof), NV = n + 6, K = m_frames.size();
+    const auto& jt = static_cast<const JointTrackingTask&>(*m_tasks[m_jointTask].task);
+    if (jt.kp().size() != n || jt.position().size() != n)
+    {
+        std::cerr << where << "The joint tracking task has " << jt.kp().size() << " joints, the model " << n
+                  << "." << std::endl;
+        return false;
+    }
+    const std::size_t oState = NV, oW = oState + 18 + 2 * n, oKp = oW + 6 * K, oPose = oKp + 2 * K,
+                      oTwist = oPose + 12 * K, oCw = oTwist + 6 * K, oCp = oCw + 3, oCv = oCp + 3,
+                      oJw = oCv + 3, oJk = oJw + n, oJp = oJk + n, oJv = oJp + n, total = oJv + n;
+    std::vector<double> host(total, 0.0);
+    double* st = host.data() + oState;
+    for (int i = 0; i < 3; ++i) st[6 + n + i] = m_basePosition[i];
+    for (int i = 0; i < 9; ++i) st[9 + n + i] = m_baseRotation[i];
+    for (std::size_t i = 0; i < n; ++i) st[18 + n + i] = m_jointPositions[i];
+    std::size_t k = 0;
+    for (const Entry& e : m_tasks)
+    {
+        if (e.task->kind() != IKLinearTask::Kind::SE3) continue;
+        const auto& se3 = static_cast<const SE3Task&>(*e.task);
+        std::copy(e.weight.begin(), e.weight.end(), host.begin() + oW + 6 * k);
+        host[oKp + 2 * k] = se3.kpLinear();
+        host[oKp + 2 * k + 1] = se3.kpAngular();
+        const auto packed = se3.pose().packed();
+        std::copy(packed.begin(), packed.end(), host.begin() + oPose + 12 * k);
+        std::copy(se3.mixedVelocity().begin(), se3.mixedVelocity().end(), host.begin() + oTwist + 6 * k);
+        ++k;
+    }
+    double comKp = 0.0;
+    if (m_comTask >= 0)
+    {
+        const auto& com = static_cast<const CoMTask&>(*m_tasks[m_comTask].task);
+        std::copy(m_tasks[m_comTask].weight.begin(), m_tasks[m_comTask].weight.end(), host.begin() + oCw);
+        std::copy(com.position().begin(), com.position().end(), host.begin() + oCp);
+        std::copy(com.velocity().begin(), com.velocity().end(), host.begin() + oCv);
+        comKp = com.kpLinear();
+    }
+    std::copy(m_tasks[m_jointTask].weight.begin(), m_tasks[m_jointTask].weight.end(), host.begin() + oJw);
+    std::copy(jt.kp().begin(), jt.kp().end(), host.begin() + oJk);
+    for (std::size_t i = 0; i < n; ++i)
+    {
+        host[oJp + i] = jt.position()[i];
+        host[oJv + i] = jt.velocity()[i];
+    }
+    std::vector<int32_t> ints(m_frames);
+    ints.push_back(0);
+    blf_handle* h = blf::threadHandle();
+    if (h == nullptr)
+    {
+        std::cerr << where << "No device." << std::endl;
+        return false;
+    }
+    if (!m_dData.upload(host) || !m_dInt.upload(ints)) return false;
+
+    double* d = m_dData.data();
+    m_cModel = blf_fb_model{};
+    m_cModel.ndof = m_model.ndof;
+    m_cModel.nframes = static_cast<int32_t>(m_model.frameLink.size());
+    m_cModel.parent = m_dParent.data();
+    m_cModel.joint_origin = m_dOrigin.data();
+    m_cModel.joint_rot = m_dRot.data();
+    m_cModel.joint_axis = m_dAxis.data();
+    m_cModel.link_mass = m_dMass.data();
+    m_cModel.link_com = m_dCom.data();
+    m_cModel.link_inertia = m_dInertia.data();
+    m_cModel.frame_link = m_dFrameLink.data();
+    m_cModel.frame_pose = m_dFramePose.data();
+    m_cModel.gravity[2] = -9.81;
+    m_cModel.rho = 0.01;
+    m_cModel.joint_type = m_model.jointType.empty() ? nullptr : m_dJointType.data();
+    m_cState = blf_fb_state{d + oState, d + oState + 6, d + oState + 6 + n, d + oState + 9 + n,
+                            d + oState + 18 + n};
+    m_cTasks = blf_ik_tasks{};
+    m_cTasks.nse3 = static_cast<int32_t>(K);
+    m_cTasks.frame = m_dInt.data();
+    m_cTasks.se3_weight = d + oW;
+    m_cTasks.se3_kp = d + oKp;
+    m_cTasks.se3_pose = d + oPose;
+    m_cTasks.se3_twist = d + oTwist;
+    m_cTasks.com_weight = m_comTask >= 0 ? d + oCw : nullptr;
+    m_cTasks.com_kp = comKp;
+    m_cTasks.com_pos = d + oCp;
+    m_cTasks.com_vel = d + oCv;
+    m_cTasks.joint_weight = d + oJw;
+    m_cTasks.joint_kp = d + oJk;
+    m_cTasks.joint_pos = d + oJp;
+    m_cTasks.joint_vel = d + oJv;
+    m_cTasks.base_damping = m_baseDamping;
+    int32_t* status = m_dInt.data() + K;
+    if (!blf::report(blf_fb_ik_solve(h, &m_cModel, &m_cState, &m_cTasks, 1, d, status, nullptr),
+                     "QPInverseKinematics::advance"))
+        return false;
+    std::vector<double> nu(NV);
+    if (!m_dData.download(nu.data(), NV) || !m_dInt.download(ints.data(), K + 1)) return false;
+    if (ints[K] != BLF_IK_OK)
+    {
+        std::cerr << where
+                  << (ints[K] == BLF_IK_BAD_INPUT ? "The robot state or a set point is not finite."
+                                                  : "The problem is not positive definite.")
+                  << std::endl;
+        return false;
+    }
+    for (int i = 0; i < 6; ++i) m_state.baseVelocity[i] = nu[i];
+    m_state.jointVelocity.resize(n);
+    for (std::size_t i = 0; i < n; ++i) m_state.jointVelocity[i] = nu[6 + i];
+    m_isValid = true;
+    return true;
+}

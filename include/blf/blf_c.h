@@ -692,6 +692,89 @@ blf_status blf_so3_eval(blf_handle* handle, const double* R0, const double* R1,
                         const double* duration, int64_t batch, const double* tq, int32_t nq,
                         double* rot, double* omega, double* alpha, void* stream);
 
+/* ---- 12. Whole-body inverse kinematics (IK::QPInverseKinematics with SE3Task, CoMTask and
+ *          JointTrackingTask, integrated by ForwardEuler<FloatingBaseSystemKinematics>), batched ----
+ * Upstream's QPInverseKinematics with every task at priority 1 (weighted): the unconstrained
+ * least-squares problem of one robot is solved in closed form.  The unknown is nu = (base mixed
+ * twist, s_dot) in R^(6+n); the kinematics are taken at state->base_pos, base_rot and joint_pos (the
+ * velocity fields of `state` are not read by blf_fb_ik_solve).  With p_B the base position, z_j /
+ * o_j joint j's world axis / origin and anc(l) the joints between the base and link l:
+ *   point Jacobian of a point x of link l (6 x (6+n), rows linear xyz then angular xyz):
+ *     base linear column a:   (e_a, 0);    base angular column a:  (e_a x (x - p_B), e_a);
+ *     joint j in anc(l):      revolute (z_j x (x - o_j), z_j), prismatic (z_j, 0);  otherwise 0.
+ *   SE3 task k on frame f_k with world pose (p, R): J_k = the point Jacobian at p;
+ *     v*_k = (v_ff + kp_lin (p_des - p),  w_ff + kp_ang (theta u)),  theta u = Log(R_des R^T) by
+ *     section 11's Log (no small-angle branch other than nv == 0).
+ *   CoM task: c_l = p_l + R_l com_l, m = sum_l m_l, c = (sum_l m_l c_l) / m (links in index order);
+ *     for joint j, m_sub = sum of m_l and h_sub = sum of m_l c_l over the links l with j in anc(l)
+ *     (index order): column j = z_j x ((h_sub - m_sub o_j) / m) (revolute), z_j (m_sub / m)
+ *     (prismatic); base columns (e_a, and e_a x (c - p_B));  v*_c = cdot_des + com_kp (c_des - c).
+ *   Joint task: sdot*_j = sdot_des_j + joint_kp_j (s_des_j - s_j).
+ *   With the task rows a_r (row r of the stacked J_k, then J_c), their weights w_r and targets t_r:
+ *     H = sum_r w_r a_r^T a_r + diag(base_damping x 6, joint_weight),
+ *     g = sum_r w_r a_r t_r + (0_6, joint_weight o sdot*),
+ *   both accumulated over r in that order with fused multiply-adds (rows of zero weight are
+ *   skipped), the diagonal term added last; H nu = g by the Cholesky factorization and the two
+ *   substitutions of the floating-base dynamics' mass-matrix path.  Device results agree with a
+ *   float64 restatement to rounding (tests/ik_reference.py, 1e-9 relative), not bit for bit.
+ * Per-robot status (status [B], may be NULL) and failures, none of which reads out of bounds or
+ * touches another robot:
+ *   BLF_IK_BAD_INPUT     a frame index outside [0, model->nframes) (the indices are shared, so
+ *                        then every robot), or a non-finite value among the robot's base_pos,
+ *                        base_rot, joint_pos or set points: nu = NaN;
+ *   BLF_IK_NOT_POSITIVE  a Cholesky pivot that is not a finite positive number: nu = NaN.
+ *   An unknown joint_type makes every robot's nu NaN (status BLF_IK_NOT_POSITIVE).
+ * blf_fb_ik_integrate: `steps` iterations in one launch with the set points held; each solves at
+ *   the current state and takes blf_fbk_euler_integrate's single step of dT with that nu as input
+ *   (p += v dT, R += dR dT with section 7's dR and model->rho, s += s_dot dT), in place on
+ *   base_pos, base_rot and joint_pos; base_vel and joint_vel receive the last step's nu.  The
+ *   result is bit for bit that of `steps` x { blf_fb_ik_solve; blf_fbk_euler_integrate(0, dT, dT) }.
+ *   A robot whose step fails keeps the state before that step, skips its remaining steps, keeps
+ *   that status (the first non-zero one) and gets a NaN nu.
+ * Call-level errors: null handle, model, state, tasks or a required pointer, reserved != 0,
+ * negative batch, steps < 1, dT not finite or not positive, a non-finite or negative weight, kp or
+ * base_damping, a non-positive joint_weight: BLF_ERR_INVALID_ARGUMENT; nse3 outside
+ * [0, BLF_IK_MAX_SE3_TASKS] or ndof outside [1, BLF_FBD_MAX_DOFS]: BLF_ERR_UNSUPPORTED;
+ * batch == 0: BLF_OK.  The shared weight and gain arrays (se3_weight, se3_kp, com_weight,
+ * joint_weight, joint_kp) are checked on the host through a staged copy: both calls copy them from
+ * the device on `stream` and wait for that copy before they launch (so neither call can be
+ * captured into a graph). */
+#define BLF_IK_MAX_SE3_TASKS 4
+#define BLF_IK_OK            0
+#define BLF_IK_NOT_POSITIVE  1   /* a Cholesky pivot was not a finite positive number */
+#define BLF_IK_BAD_INPUT     2   /* frame index out of range, or a non-finite state / set point of this robot */
+typedef struct blf_ik_tasks {
+    int32_t nse3;               /* K, 0..BLF_IK_MAX_SE3_TASKS                                   */
+    int32_t reserved;           /* must be 0                                                    */
+    const int32_t* frame;       /* [K] frame indices of the model                               */
+    const double* se3_weight;   /* [K][6] row weights (linear xyz, angular xyz), finite, >= 0;
+                                   a zero drops the row: linear zeros = SO3Task, angular zeros = R3Task */
+    const double* se3_kp;       /* [K][2] (kp_linear, kp_angular)                               */
+    const double* se3_pose;     /* [B][K][12] desired (p, R row-major): blf_swing_foot_eval's
+                                   pose output for L = B*K lists, Q = 1, as it stands           */
+    const double* se3_twist;    /* [B][K][6] feed-forward mixed twist, or NULL (zero)            */
+    const double* com_weight;   /* [3] or NULL: no CoM task                                     */
+    double com_kp;
+    const double* com_pos;      /* [B][3]; required iff com_weight                              */
+    const double* com_vel;      /* [B][3] or NULL (zero)                                        */
+    const double* joint_weight; /* [n], finite, > 0 (JointTrackingTask: the regulariser)        */
+    const double* joint_kp;     /* [n]                                                          */
+    const double* joint_pos;    /* [B][n] desired joint positions                               */
+    const double* joint_vel;    /* [B][n] or NULL (zero)                                        */
+    double base_damping;        /* finite, >= 0: added to the six base diagonal entries of H    */
+} blf_ik_tasks;
+
+blf_status blf_fb_ik_solve(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                           const blf_ik_tasks* tasks, int64_t batch, double* nu /* [B][6+n] */,
+                           int32_t* status /* [B] or NULL */, void* stream);
+
+blf_status blf_fb_ik_integrate(blf_handle* handle, const blf_fb_model* model,
+                               const blf_fb_state* state /* in place */, const blf_ik_tasks* tasks,
+                               int64_t batch, int32_t steps, double dT,
+                               double* nu /* [B][6+n], the last step's, or NULL */,
+                               int32_t* status /* [B] or NULL: the first non-zero of the steps */,
+                               void* stream);
+
 /* Algorithmic flop count of one IPM iteration of one problem (what the fp64 roofline field
  * of bench.py is computed from); `active_facets` = sum_k nfacets[k]. */
 double blf_dcm_mpc_flops_per_iter(int32_t horizon, int64_t active_facets);

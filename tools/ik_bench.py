@@ -1,0 +1,148 @@
+"""Timing of the whole-body IK kernel (csrc/fb_ik.hip) on the humanoid's standing task set
+(diagnostics; not the driver's bench.py).  HIP events around `reps` back-to-back calls after a
+warm-up, median of `rounds` rounds, the variants alternating within a round.  One JSON line each:
+
+  * blf_fb_ik_solve at B robots: time per call, the counted flops per robot (below) over time as a
+    fraction of the vector fp64 peak;
+  * blf_fb_ik_integrate with steps = 20 (the state restored before every call by a device copy,
+    timed on its own and reported), and the unfused sequence it replaces: 20 x { blf_fb_ik_solve;
+    blf_fbk_euler_integrate(0, dT, dT) with that nu }; the fused / unfused ratio;
+  * as yardsticks at the same B, the two existing kernels the IK is assembled from:
+    blf_fb_frame_state (the forward kinematics alone, one robot per wavefront) and blf_fbd_dynamics
+    with mass_reg = zeros and no contacts (kinematics, mass matrix, the same Cholesky and
+    substitutions, two robots per wavefront).
+
+Counted flops per robot-step, NV = n + 6, M = the task rows of non-zero weight: H and g from the task
+rows M (NV (NV + 1) + 2 NV), the Cholesky factorization NV^3 / 3, the two substitutions 2 NV^2.  The
+kinematics and the task rows themselves are not counted.  Both calls stage the shared weight arrays
+to the host and wait for that copy before they launch (blf_c.h section 12), so every call here
+includes one stream synchronisation: the unfused sequence pays 20 of them, the fused call one.
+
+  timeout -k 10 600 python tools/ik_bench.py [--robots 16384] [--steps 20] [--rounds 5]
+(BLF_LIB=.../lib/libblf_<name>.so times a variant build, tools/build_variant.sh)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "bipedal-locomotion-framework_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from blf import native, robot  # noqa: E402
+
+FP64_PEAK = 78.6e12   # MI355X vector fp64, flop/s
+DT = 0.01
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps   # ms per call
+
+
+def compare(variants, reps, rounds):
+    """{name: fn} -> {name: [median ms, min ms, max ms]}, the variants alternating in every round."""
+    for fn in variants.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(timed(fn, reps))
+    return {k: [statistics.median(v), min(v), max(v)] for k, v in times.items()}
+
+
+def counted_flops(NV, M):
+    return M * (NV * (NV + 1) + 2 * NV) + NV ** 3 / 3.0 + 2 * NV ** 2
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robots", type=int, default=16384)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--label", default="")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device"
+    h = native.Handle(0)
+    prov = native.build_provenance()
+    print(json.dumps({"bench": "provenance", "lib_src_hash": prov["lib_src_hash"],
+                      "lib": os.path.basename(prov["lib"]), "matches_tree": prov["matches"],
+                      "device": torch.cuda.get_device_name(0), "label": args.label}), flush=True)
+    B, steps = args.robots, args.steps
+    model = robot.humanoid24()
+    n = model["n"]
+    NV = n + 6
+    host = robot.standing_states(model, B, seed=1, spread=0.2)
+    host["joint_pos"] = host["joint_pos"] + np.random.default_rng(2).normal(size=(B, n)) * 0.05
+    tasks = robot.standing_ik_tasks(model, host)
+    M = int((tasks["se3_weight"] > 0).sum() + (tasks["com_weight"] > 0).sum())
+    dm = h.fb_model(model)
+    tk = h.ik_tasks(B, n, **tasks)
+    start = {k: torch.from_numpy(np.ascontiguousarray(host[k])).cuda() for k in native.FB_STATE_KEYS}
+    st = {k: v.clone() for k, v in start.items()}
+    nu = torch.empty((B, NV), dtype=torch.float64, device="cuda")
+    status = torch.empty((B,), dtype=torch.int32, device="cuda")
+    twist = torch.empty((B, 6), dtype=torch.float64, device="cuda")
+    jv = torch.empty((B, n), dtype=torch.float64, device="cuda")
+
+    def restore():
+        for k in native.FB_STATE_KEYS:
+            st[k].copy_(start[k])
+
+    def fused():
+        restore()
+        h.fb_ik_integrate(dm, st, tk, steps, DT, nu=nu, status=status)
+
+    def unfused():
+        restore()
+        for _ in range(steps):
+            h.fb_ik_solve(dm, st, tk, nu=nu, status=status)
+            twist.copy_(nu[:, :6])
+            jv.copy_(nu[:, 6:])
+            h.fbk_euler_integrate(dm.c.rho, st["base_pos"], st["base_rot"], st["joint_pos"], twist, jv, 0.0, DT, DT)
+
+    frames = torch.arange(len(model["frame_link"]), dtype=torch.int32, device="cuda")
+    fpose = torch.empty((B, frames.shape[0], 12), dtype=torch.float64, device="cuda")
+    ftwist = torch.empty((B, frames.shape[0], 6), dtype=torch.float64, device="cuda")
+    tau = torch.zeros((B, n), dtype=torch.float64, device="cuda")
+    reg = torch.zeros((NV, NV), dtype=torch.float64, device="cuda")
+    res = compare({"solve": lambda: h.fb_ik_solve(dm, start, tk, nu=nu, status=status), "restore": restore,
+                   "fused": fused, "unfused": unfused,
+                   "frame_state": lambda: h.fb_frame_state(dm, start, frames, pose=fpose, twist=ftwist),
+                   "fbd_dynamics_reg": lambda: h.fbd_dynamics(dm, start, tau, mass_reg=reg)},
+                  reps=args.reps, rounds=args.rounds)
+    fused()
+    f_state = {k: v.clone() for k, v in st.items()}
+    ok_f = bool((status == 0).all())
+    unfused()
+    same = all(torch.equal(f_state[k], st[k]) for k in ("base_pos", "base_rot", "joint_pos"))
+    fl = counted_flops(NV, M)
+    print(json.dumps({"bench": "fb_ik_solve", "robots": B, "ndof": n, "task_rows": M, "ms": res["solve"],
+                      "counted_flops_per_robot_step": fl,
+                      "fp64_fraction": B * fl / (res["solve"][0] * 1e-3) / FP64_PEAK,
+                      "fb_frame_state_ms": res["frame_state"], "fbd_dynamics_mass_reg_ms": res["fbd_dynamics_reg"],
+                      "label": args.label}), flush=True)
+    f_ms = res["fused"][0] - res["restore"][0]
+    u_ms = res["unfused"][0] - res["restore"][0]
+    print(json.dumps({"bench": "fb_ik_integrate", "robots": B, "steps": steps, "fused_ms": res["fused"],
+                      "unfused_ms": res["unfused"], "restore_ms": res["restore"],
+                      "fused_ms_per_step_net": f_ms / steps, "fused_over_unfused_net": f_ms / u_ms,
+                      "fp64_fraction_fused": B * steps * fl / (f_ms * 1e-3) / FP64_PEAK,
+                      "fused_equals_unfused_bitwise": same, "all_status_ok": ok_f,
+                      "label": args.label}), flush=True)
+    h.close()
+
+
+if __name__ == "__main__":
+    main()
