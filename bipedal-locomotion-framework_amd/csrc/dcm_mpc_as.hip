@@ -645,9 +645,16 @@ __device__ __forceinline__ int as_vertex_pair(const RS& R, int kx, int km, int c
 // instead evaluates exactly two quotients whose operands its case selects (c = 0: b2 / Rw0,
 // b2 / Rw1; c = 1: (a r - b) / |a|^2, b2 / (Rw0 a_y^2 + Rw1 a_x^2); c = 2: 1 / det) — the same
 // operations as the per-case form of the oracle, so the results are bit-identical.
+// The rows pi1, pi2 are constant over a pass: the float passes carry their normals (na, ne) from
+// here to as_pass_h and as_certify instead of reading and rounding the fp64 LDS rows again (3
+// ds_read_b128 and 6 v_cvt_f32_f64 per knot and pass); the fp64 passes read them again, which
+// keeps their registers free across the sweep and the solve.
+template <class T>
+constexpr bool kCarryNormals = sizeof(T) == 4;
+
 template <class T, class RS>
 __device__ __forceinline__ void as_pass_setup(AKnotT<T>& K, const PT<T>& P, const RS& R, int col, T sr0,
-                                              T sr1, int& pk, T (&E)[3], bool& okp)
+                                              T sr1, int& pk, T (&E)[3], bool& okp, Row<T>& na, Row<T>& ne)
 {
     const int cx = opaque(col);
     const int km = opaque(K.m);
@@ -664,6 +671,10 @@ __device__ __forceinline__ void as_pass_setup(AKnotT<T>& K, const PT<T>& P, cons
     const T b2 = K.be * K.be;
     const Row<T> a = row<T>(R, pi1, cx);
     const Row<T> e = row<T>(R, pi2, cx);
+    if constexpr (kCarryNormals<T>) {
+        na = a;
+        ne = e;
+    }
     const T aa = FD2(a.x, a.x, a.y, a.y);
     const T u = a.y * a.y, v = a.x * a.x, q = a.x * a.y;
     const T det = fma(a.x, e.y, -(a.y * e.x));
@@ -690,14 +701,15 @@ __device__ __forceinline__ void as_pass_setup(AKnotT<T>& K, const PT<T>& P, cons
 // operands selected by the case (bit-identical to the per-case form).
 template <class T, class RS>
 __device__ __forceinline__ void as_pass_h(AKnotT<T>& K, const PT<T>& P, const RS& R, int col, int pk,
-                                          bool& okp)
+                                          bool& okp, const Row<T>& na)
 {
     const int pc = pk & 3, pi1 = (pk >> 2) & 15;
     const T b2 = K.be * K.be;
     const T B00 = fma(b2, K.P00, P.Rw0);
     const T B01 = b2 * K.P01;
     const T B11 = fma(b2, K.P11, P.Rw1);
-    const Row<T> a = normal<T>(R, pi1, opaque(col));
+    Row<T> a = na;
+    if constexpr (!kCarryNormals<T>) a = normal<T>(R, pi1, opaque(col));
     const T u = a.y * a.y, v = a.x * a.x, q = a.x * a.y;
     const T detB = fma(B00, B11, -(B01 * B01));
     const T tbt = FD3(B00, u, B11, v, T(-2) * (B01 * q));
@@ -715,7 +727,8 @@ __device__ __forceinline__ void as_pass_h(AKnotT<T>& K, const PT<T>& P, const RS
 template <class T, class RS>
 __device__ __forceinline__ void as_certify(AKnotT<T>& K, const PT<T>& P, const RS& R, int col, int pk,
                                            T dx0, T dx1, T vn0, T vn1, T& l1o, T& l2o, bool& okp, bool& neg,
-                                           bool& viol, bool bland, int& ndrop, int& nadd)
+                                           bool& viol, bool bland, int& ndrop, int& nadd, const Row<T>& na,
+                                           const Row<T>& ne)
 {
     const int cx = opaque(col);
     const int pc = pk & 3, pi1 = (pk >> 2) & 15, pi2 = (pk >> 6) & 15;
@@ -730,8 +743,11 @@ __device__ __forceinline__ void as_certify(AKnotT<T>& K, const PT<T>& P, const R
     K.rh1 = nu1;
     const T g0 = fma(K.be, nu0, -rh0);
     const T g1 = fma(K.be, nu1, -rh1);
-    const Row<T> a = normal<T>(R, pi1, cx);
-    const Row<T> e = normal<T>(R, pi2, cx);
+    Row<T> a = na, e = ne;
+    if constexpr (!kCarryNormals<T>) {
+        a = normal<T>(R, pi1, cx);
+        e = normal<T>(R, pi2, cx);
+    }
     const T n = pc == 1 ? FD2(a.x, g0, a.y, g1) : T(1);
     const T d = pc == 1 ? FD2(a.x, a.x, a.y, a.y) : fma(a.x, e.y, -(a.y * e.x));
     const T qd = n / d;
@@ -916,6 +932,7 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
         T E[KPL][3];
         int c0[KPL];
         bool okp = true;
+        Row<T> na[KPL], ne[KPL];   // the normals of the pass's rows pi1, pi2 (kCarryNormals)
 #pragma unroll
         for (int j = 0; j < KPL; ++j) {
             const int k = KPL * lane + j;
@@ -923,7 +940,8 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
             sv[j][0] = K[j].r0; sv[j][1] = K[j].r1; sv[j][2] = K[j].x0; sv[j][3] = K[j].x1;
             E[j][0] = E[j][1] = E[j][2] = T(0);
             pk[j] = 0;
-            if (k < N) as_pass_setup<T>(K[j], P, R, R.col(j, lane), sv[j][0], sv[j][1], pk[j], E[j], okp);
+            if (k < N)
+                as_pass_setup<T>(K[j], P, R, R.col(j, lane), sv[j][0], sv[j][1], pk[j], E[j], okp, na[j], ne[j]);
         }
         AS_STAMP_ADD(sb + 0, t_s);
         AS_STAMP(t_r);
@@ -934,7 +952,7 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
         for (int j = 0; j < KPL; ++j) {
             const int k = KPL * lane + j;
             if (k < N) {
-                as_pass_h<T>(K[j], P, R, R.col(j, lane), opaque(pk[j]), okp);
+                as_pass_h<T>(K[j], P, R, R.col(j, lane), opaque(pk[j]), okp, na[j]);
                 // the residuals at the projected point (after the sweep, which does not read them)
                 as_residuals(K[j], P, k == N - 1, xk[j][0], xk[j][1]);
             }
@@ -966,7 +984,7 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
                     K[j].x1 = K[j].x1 + dx[j][1];
                     if constexpr (sizeof(T) == 8) as_project<T>(K[j], R, R.col(j, lane), opaque(pk[j]));
                     as_certify<T>(K[j], P, R, R.col(j, lane), opaque(pk[j]), dx[j][0], dx[j][1], vn[j][0], vn[j][1],
-                                  pl[j][0], pl[j][1], okp, neg, viol, kAnti && bland, ndr[j], nad[j]);
+                                  pl[j][0], pl[j][1], okp, neg, viol, kAnti && bland, ndr[j], nad[j], na[j], ne[j]);
                 }
             }
             AS_STAMP_ADD(sb + 4, t_c);
@@ -1032,10 +1050,66 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
 // Stages the QP's facet slabs A [N][M][2], b [N][M] into LDS ([M][S] normals, [M][S] offsets,
 // facet i of knot k at i S + (k % KPL) NH + k / KPL), in the scalar type V: coalesced loads
 // (consecutive lanes on consecutive 16 B), U per lane in flight before the LDS stores.
+//
+// The fast path: when 64 % (M KPL) == 0 (M a power of two up to 64 / KPL) and t0 is a multiple of
+// 64, a lane's element t = t0 + 64 u + lane keeps its facet i = lane % M from round to round, its
+// knot advances by 64 / M, a multiple of KPL, and its LDS slot by 64 / (M KPL).  So i, the knot's
+// slot and the global addresses are computed once per lane and round u is a constant offset from
+// them: no per-round multiply, divide or clamp.  A lane loads and stores only its elements below
+// nA, so the rounds wholly past nA are skipped by the wavefront (exec is empty), loads included.
+// Same values into the same slots as the generic path.
+template <int KPL>
+__device__ __forceinline__ bool stage_rows_fast(int M, int t0)
+{
+    return M > 0 && kWave % (M * KPL) == 0 && t0 % kWave == 0;
+}
+
 template <int U>
-__device__ __forceinline__ void stage_rows_issue(const double* Ain, const double* bin, int64_t p, int lane,
+__device__ __forceinline__ void stage_rows_issue_fast(const double* Ain, const double* bin, int64_t p, int lane,
+                                                      int t0, int nA, double2 (&va)[U], double (&vb)[U])
+{
+    typedef double d2v __attribute__((ext_vector_type(2)));
+    const d2v* As = reinterpret_cast<const d2v*>(Ain) + p * nA + t0;   // wave-uniform
+    const double* bs = bin + p * nA + t0;
+    const int left = opaque(nA - t0 - lane);   // the lane's elements: rounds u with 64 u < left
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (u * kWave < left) {
+            // a wave-uniform base per round plus the lane: scalar adds, one 32-bit lane offset
+            const d2v w = __builtin_nontemporal_load(As + u * kWave + (unsigned)lane);
+            va[u] = make_double2(w.x, w.y);
+            vb[u] = __builtin_nontemporal_load(bs + u * kWave + (unsigned)lane);
+        }
+    }
+}
+
+// MC: M at compile time (the launch's facet slots: the rounds' LDS offsets are immediates), or 0
+template <int KPL, int U, int MC, class V>
+__device__ __forceinline__ void stage_rows_commit_fast(const double2 (&va)[U], const double (&vb)[U], int Mrt,
+                                                       int S, int NH, int lane, int t0, int nA, V* A2v, V* Bv)
+{
+    const int M = MC ? MC : Mrt;
+    const int step = kWave / (M * KPL);   // LDS slots per round
+    const int i = lane & (M - 1), kl = lane >> __builtin_ctz(M);
+    const int o0 = (int)__umul24((unsigned)i, (unsigned)S) + (kl % KPL) * NH + kl / KPL + (t0 / kWave) * step;
+    V* const A0 = A2v + 2 * o0;
+    V* const B0 = Bv + o0;
+    const int left = opaque(nA - t0 - lane);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (u * kWave < left) {
+            A0[2 * u * step] = V(va[u].x);
+            A0[2 * u * step + 1] = V(va[u].y);
+            B0[u * step] = V(vb[u]);
+        }
+    }
+}
+
+template <int KPL, int U>
+__device__ __forceinline__ void stage_rows_issue(const double* Ain, const double* bin, int64_t p, int M, int lane,
                                                  int t0, int nA, double2 (&va)[U], double (&vb)[U])
 {
+    if (stage_rows_fast<KPL>(M, t0)) return stage_rows_issue_fast<U>(Ain, bin, p, lane, t0, nA, va, vb);
     const double2* As = reinterpret_cast<const double2*>(Ain) + p * nA;
     const double* bs = bin + p * nA;
 #pragma unroll
@@ -1050,10 +1124,17 @@ __device__ __forceinline__ void stage_rows_issue(const double* Ain, const double
     }
 }
 
-template <int KPL, int U, class V>
+// MF: the launch's facet slots when the caller has them (M == MF takes the fast path with M at
+// compile time), or 0
+template <int KPL, int U, class V, int MF = 0>
 __device__ __forceinline__ void stage_rows_commit(const double2 (&va)[U], const double (&vb)[U], int M, int S,
                                                   int NH, int lane, int t0, int nA, V* A2v, V* Bv)
 {
+    if (stage_rows_fast<KPL>(M, t0)) {
+        if (MF != 0 && M == MF)
+            return stage_rows_commit_fast<KPL, U, MF, V>(va, vb, M, S, NH, lane, t0, nA, A2v, Bv);
+        return stage_rows_commit_fast<KPL, U, 0, V>(va, vb, M, S, NH, lane, t0, nA, A2v, Bv);
+    }
     const bool pow2 = (M & (M - 1)) == 0;
     const int sh = __builtin_ctz(M);
 #pragma unroll
@@ -1069,14 +1150,14 @@ __device__ __forceinline__ void stage_rows_commit(const double2 (&va)[U], const 
     }
 }
 
-template <int KPL, int U, class V>
+template <int KPL, int U, class V, int MF = 0>
 __device__ __forceinline__ void stage_rows(const double* Ain, const double* bin, int64_t p, int N, int M, int S,
                                            int NH, int lane, int t0, int nA, V* A2v, V* Bv)
 {
     double2 va[U];
     double vb[U];
-    stage_rows_issue<U>(Ain, bin, p, lane, t0, nA, va, vb);
-    stage_rows_commit<KPL, U, V>(va, vb, M, S, NH, lane, t0, nA, A2v, Bv);
+    stage_rows_issue<KPL, U>(Ain, bin, p, M, lane, t0, nA, va, vb);
+    stage_rows_commit<KPL, U, V, MF>(va, vb, M, S, NH, lane, t0, nA, A2v, Bv);
 }
 
 // ---- the phase-indexed input (blf_dcm_mpc_solve_phased) ----
@@ -1148,12 +1229,12 @@ __device__ __forceinline__ void stage_rows_ph(const PhaseSrc& ps, const int32_t*
 }
 
 // The QP's rows into LDS in rounds of U loads per lane (the 16-slot instantiations).
-template <int KPL, int U>
+template <int KPL, int U, int MF>
 __device__ __forceinline__ void stage_rows_rounds(const double* Ain, const double* bin, int64_t p, int N, int M,
                                                   int S, int NH, int lane, double* A2v, double* Bv)
 {
     for (int t0 = 0; t0 < N * M; t0 += U * kWave)
-        stage_rows<KPL, U, double>(Ain, bin, p, N, M, S, NH, lane, t0, N * M, A2v, Bv);
+        stage_rows<KPL, U, double, MF>(Ain, bin, p, N, M, S, NH, lane, t0, N * M, A2v, Bv);
 }
 
 // A knot's own inputs: facet count, omega, references (vrp_ref_k, xi_ref_{k+1}).
@@ -1320,7 +1401,7 @@ __device__ __forceinline__ void cold_solve(
         ph_stage_phases(ps, p, N, P.dt, lane, sBE, sPh);
         stage_rows_ph<KPL, U, kWide>(ps, sPh, p, N, M, S, NH, lane, A2d, Bv);
     } else if (kWide) {
-        stage_rows_rounds<KPL, U>(Ain, bin, p, N, M, S, NH, lane, A2d, Bv);
+        stage_rows_rounds<KPL, U, MF>(Ain, bin, p, N, M, S, NH, lane, A2d, Bv);
     }
     // kOverlap: issued below, after the knot loads: a wait for those (vmcnt counts in issue order)
     // then leaves the younger row loads in flight
@@ -1363,12 +1444,12 @@ __device__ __forceinline__ void cold_solve(
         Fj.x0 = Fj.xr0; Fj.x1 = Fj.xr1;
     }
     const float xf00 = float(xi00), xf01 = float(xi01);
-    if (kOverlap) stage_rows_issue<U>(Ain, bin, p, lane, 0, nA, va, vb);
+    if (kOverlap) stage_rows_issue<KPL, U>(Ain, bin, p, M, lane, 0, nA, va, vb);
     AS_STAMP_ADD(1, t_start);
     {
         AS_STAMP(t_q);
         as_lq_step<KPL, TR, float>(F, Pf, N, lane, xf00, xf01);
-        if (kOverlap) stage_rows_commit<KPL, U, double>(va, vb, M, S, NH, lane, 0, nA, A2d, Bv);
+        if (kOverlap) stage_rows_commit<KPL, U, double, MF>(va, vb, M, S, NH, lane, 0, nA, A2d, Bv);
         __syncthreads();   // the LDS rows (one wavefront: a wait for the stores)
         AS_STAMP_ADD(2, t_q);
         AS_STAMP(t_g);
@@ -1439,8 +1520,10 @@ __device__ __forceinline__ void cold_solve(
         // the fp64 passes' guess: the facets active at a certified float point (slack below
         // kGuessSlack); when the search stopped uncertified, its next candidate sets
         const double* const lw0[KPL] = {};
-        as_guess<KPL, double>(K, R, NH, N, lane, lw0, 0.0, kGuessSlack);
-        if (!cert32) {
+        // (cert32 comes from a ballot: wave-uniform, so the uncertified hand-over skips the rows' reads)
+        if (cert32) {
+            as_guess<KPL, double>(K, R, NH, N, lane, lw0, 0.0, kGuessSlack);
+        } else {
 #pragma unroll
             for (int j = 0; j < KPL; ++j) K[j].gm = KPL * lane + j < N ? cand[j] : 0;
         }
@@ -1561,7 +1644,7 @@ __global__ __launch_bounds__(kWave, kAsMinWaves) void dcm_mpc_warm_kernel(
     if (PH) ph_stage_phases(ps, p, N, P.dt, lane, sBE, sPh);
     if constexpr (kWide) {
         if (PH) stage_rows_ph<KPL, U, true>(ps, sPh, p, N, M, S, NH, lane, reinterpret_cast<double*>(A2), Bv);
-        else stage_rows_rounds<KPL, U>(Ain, bin, p, N, M, S, NH, lane, reinterpret_cast<double*>(A2), Bv);
+        else stage_rows_rounds<KPL, U, MF>(Ain, bin, p, N, M, S, NH, lane, reinterpret_cast<double*>(A2), Bv);
     }
     // the rows' loads are issued after the knots' loads (vmcnt counts in issue order) and land in
     // LDS after the warm start's rollout, which does not read them
@@ -1593,7 +1676,7 @@ __global__ __launch_bounds__(kWave, kAsMinWaves) void dcm_mpc_warm_kernel(
     }
     if constexpr (!kWide) {
         if (PH) stage_rows_ph_issue<U>(ps, sPh, p, N, M, lane, va, vb);
-        else stage_rows_issue<U>(Ain, bin, p, lane, 0, nA, va, vb);
+        else stage_rows_issue<KPL, U>(Ain, bin, p, M, lane, 0, nA, va, vb);
     }
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
@@ -1649,7 +1732,7 @@ __global__ __launch_bounds__(kWave, kAsMinWaves) void dcm_mpc_warm_kernel(
             K[j].x1 = x[j][1];
         }
     }
-    if constexpr (!kWide) stage_rows_commit<KPL, U, double>(va, vb, M, S, NH, lane, 0, nA, reinterpret_cast<double*>(A2), Bv);
+    if constexpr (!kWide) stage_rows_commit<KPL, U, double, MF>(va, vb, M, S, NH, lane, 0, nA, reinterpret_cast<double*>(A2), Bv);
     __syncthreads();   // the LDS slabs (one wavefront: a wait for the stores)
     AS_STAMP_ADD(2, t_lq);
     if (any_bad) {
