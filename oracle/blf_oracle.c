@@ -2112,6 +2112,16 @@ int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, con
                            double* xi, double* vrp, double* lam_out, int32_t* iters_out,
                            int32_t* polished_out, int32_t* passes_out)
 {
+    return orc_dcm_mpc_solve_warm64(prm, xi_init, omega, xi_ref, vrp_ref, Ain, bin, nfacets, warm, xi, vrp,
+                                    lam_out, iters_out, polished_out, passes_out, NULL);
+}
+
+int orc_dcm_mpc_solve_warm64(const orc_dcm_params* prm, const double* xi_init, const double* omega,
+                             const double* xi_ref, const double* vrp_ref, const double* Ain,
+                             const double* bin, const int32_t* nfacets, const orc_dcm_warm* warm,
+                             double* xi, double* vrp, double* lam_out, int32_t* iters_out,
+                             int32_t* polished_out, int32_t* passes_out, int32_t* passes64_out)
+{
     const int N = prm->horizon;
     const int M = prm->max_facets;
     dcm_ws ws;
@@ -2149,6 +2159,7 @@ int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, con
 
     int status = 0, it = 0, ntot = 0, polished = 0;
     int as_passes = 0;   /* the active-set kernels' drop/add passes (blf_dcm_mpc_solution.passes) */
+    int as_passes64 = 0; /* their fp64 passes alone (as_passes less a cold start's fp32 search) */
     w->npass = 0;
     for (int k = 0; k < N; ++k) {
         if (nfacets[k] < 0 || nfacets[k] > M) status = 3;
@@ -2224,6 +2235,7 @@ int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, con
         }
         const int okg = dcm_polish(w, prm->tol_primal, prm->tol_dual, g32, ORC_AS_PASSES, 1);
         as_passes = np32 + w->npass;
+        as_passes64 = w->npass;
         free(r32);
         free(g32);
         if (okg) { polished = 1; status = 0; it = 0; goto done; }
@@ -2273,7 +2285,7 @@ int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, con
         }
         const int okg = dcm_polish(w, prm->tol_primal, prm->tol_dual, gm, as_kernel ? ORC_AS_PASSES : ORC_GUESS_PASSES,
                                    as_kernel);
-        if (as_kernel) as_passes = w->npass;   /* the warm kernel's passes */
+        if (as_kernel) as_passes = as_passes64 = w->npass;   /* the warm kernel's passes */
         free(gm);
         if (okg) { polished = 1; status = 0; it = 0; goto done; }
         if (warm && as_kernel) {
@@ -2281,8 +2293,8 @@ int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, con
              * passes do not certify is solved again from a cold start (fp32 search, fp64 passes),
              * and the interior point method, if it still needs it, starts cold (kPendingCold) */
             free(mem);
-            return orc_dcm_mpc_solve_warm(prm, xi_init, omega, xi_ref, vrp_ref, Ain, bin, nfacets, NULL, xi,
-                                          vrp, lam_out, iters_out, polished_out, passes_out);
+            return orc_dcm_mpc_solve_warm64(prm, xi_init, omega, xi_ref, vrp_ref, Ain, bin, nfacets, NULL, xi,
+                                            vrp, lam_out, iters_out, polished_out, passes_out, passes64_out);
         }
     }
     /* the interior point method's own start (only when the active-set start did not certify):
@@ -2475,6 +2487,7 @@ done:
     if (iters_out) *iters_out = it;
     if (polished_out) *polished_out = polished;
     if (passes_out) *passes_out = as_passes;
+    if (passes64_out) *passes64_out = as_passes64;
 #ifdef ORC_STATS   /* diagnostic builds only: the solve's IPM iterations and all polish passes */
     fprintf(stderr, "ORC_STATS it %d as_passes %d all_polish_passes %d status %d\n", it, as_passes, w->npass, status);
 #endif
@@ -2498,7 +2511,7 @@ typedef struct {
     int32_t shift;
     double floor;
     double *xi, *vrp, *lam_out;
-    int32_t *status, *iters, *polished, *passes;
+    int32_t *status, *iters, *polished, *passes, *passes64;
     atomic_llong next;
 } batch_job;
 
@@ -2520,13 +2533,14 @@ static void* batch_worker(void* arg)
             wm.floor = J->floor;
             wp = &wm;
         }
-        J->status[p] = orc_dcm_mpc_solve_warm(
+        J->status[p] = orc_dcm_mpc_solve_warm64(
             J->prm, J->xi_init + 2 * p, J->omega + (int64_t)N * p,
             J->xi_ref + (int64_t)2 * (N + 1) * p, J->vrp_ref + (int64_t)2 * N * p,
             J->A + (int64_t)2 * N * M * p, J->b + (int64_t)N * M * p, J->nfacets + (int64_t)N * p,
             wp, J->xi + (int64_t)2 * (N + 1) * p, J->vrp + (int64_t)2 * N * p,
             J->lam_out ? J->lam_out + (int64_t)N * M * p : NULL, J->iters + p,
-            J->polished ? J->polished + p : NULL, J->passes ? J->passes + p : NULL);
+            J->polished ? J->polished + p : NULL, J->passes ? J->passes + p : NULL,
+            J->passes64 ? J->passes64 + p : NULL);
     }
     return NULL;
 }
@@ -2562,11 +2576,25 @@ void orc_dcm_mpc_solve_batch_warm(const orc_dcm_params* prm, int64_t batch, int 
                                   double floor, double* xi, double* vrp, double* lam_out,
                                   int32_t* status, int32_t* iters, int32_t* polished, int32_t* passes)
 {
+    orc_dcm_mpc_solve_batch_warm64(prm, batch, threads, xi_init, omega, xi_ref, vrp_ref, A, b, nfacets, vrp_ws,
+                                   lam_ws, prev_status, shift, floor, xi, vrp, lam_out, status, iters, polished,
+                                   passes, NULL);
+}
+
+void orc_dcm_mpc_solve_batch_warm64(const orc_dcm_params* prm, int64_t batch, int threads,
+                                    const double* xi_init, const double* omega, const double* xi_ref,
+                                    const double* vrp_ref, const double* A, const double* b,
+                                    const int32_t* nfacets, const double* vrp_ws,
+                                    const double* lam_ws, const int32_t* prev_status, int32_t shift,
+                                    double floor, double* xi, double* vrp, double* lam_out,
+                                    int32_t* status, int32_t* iters, int32_t* polished, int32_t* passes,
+                                    int32_t* passes64)
+{
     batch_job J = {.prm = prm, .batch = batch, .xi_init = xi_init, .omega = omega,
                    .xi_ref = xi_ref, .vrp_ref = vrp_ref, .A = A, .b = b, .nfacets = nfacets,
                    .vrp_ws = vrp_ws, .lam_ws = lam_ws, .prev_status = prev_status, .shift = shift,
                    .floor = floor,
                    .xi = xi, .vrp = vrp, .lam_out = lam_out, .status = status, .iters = iters,
-                   .polished = polished, .passes = passes};
+                   .polished = polished, .passes = passes, .passes64 = passes64};
     run_batch(&J, threads);
 }

@@ -145,6 +145,15 @@ int orc_dcm_mpc_solve_warm(const orc_dcm_params* prm, const double* xi_init, con
                            const double* b, const int32_t* nfacets, const orc_dcm_warm* warm,
                            double* xi, double* vrp, double* lam_out, int32_t* iters,
                            int32_t* polished, int32_t* passes);
+/* The same solve with one more optional output: the fp64 passes alone (passes less a cold start's
+ * fp32 search; the anti-cycling rule of dcm_polish moves from the 10th on) to *passes64 (NULL: not
+ * written; no device output corresponds to it).  A separate entry point, so that callers bound to
+ * orc_dcm_mpc_solve_warm's argument list keep working. */
+int orc_dcm_mpc_solve_warm64(const orc_dcm_params* prm, const double* xi_init, const double* omega,
+                             const double* xi_ref, const double* vrp_ref, const double* A,
+                             const double* b, const int32_t* nfacets, const orc_dcm_warm* warm,
+                             double* xi, double* vrp, double* lam_out, int32_t* iters,
+                             int32_t* polished, int32_t* passes, int32_t* passes64);
 
 /* Whole batch (problem-major arrays), split over `threads` POSIX threads (one problem per
  * thread at a time).  Used as bench.py's CPU baseline. */
@@ -164,6 +173,15 @@ void orc_dcm_mpc_solve_batch_warm(const orc_dcm_params* prm, int64_t batch, int 
                                   const double* lam_ws, const int32_t* prev_status, int32_t shift,
                                   double floor, double* xi, double* vrp, double* lam_out,
                                   int32_t* status, int32_t* iters, int32_t* polished, int32_t* passes);
+/* orc_dcm_mpc_solve_batch_warm over orc_dcm_mpc_solve_warm64: also passes64 [B] or NULL. */
+void orc_dcm_mpc_solve_batch_warm64(const orc_dcm_params* prm, int64_t batch, int threads,
+                                    const double* xi_init, const double* omega, const double* xi_ref,
+                                    const double* vrp_ref, const double* A, const double* b,
+                                    const int32_t* nfacets, const double* vrp_ws,
+                                    const double* lam_ws, const int32_t* prev_status, int32_t shift,
+                                    double floor, double* xi, double* vrp, double* lam_out,
+                                    int32_t* status, int32_t* iters, int32_t* polished, int32_t* passes,
+                                    int32_t* passes64);
 
 /* Tree sum with the device's reduction order: c has n entries, padded with
  * zeros to 64*ceil(n/64); per 64-block xor-butterfly (distances 1, 2, 4, ..., 32), then block

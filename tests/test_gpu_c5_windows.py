@@ -33,9 +33,10 @@ def test_c5_windows_warm_bitwise(handle, oracle, name):
                 shift=1, floor=1e-3, status=torch.from_numpy(d["prev_status"]).cuda())
     out = handle.dcm_mpc_solve(dev, prm, warm=warm, lambda_out=True)
     torch.cuda.synchronize()
+    pas = np.zeros(B, np.int32)
     st, xi, vrp, it, lam = oracle.dcm_mpc_solve_batch_warm(
         prob, vrp_ws=d["vrp_ws"], lam_ws=d["lam_ws"], shift=1, floor=1e-3,
-        params=oracle.default_params(N, tol_polish=1e-4), prev_status=d["prev_status"], threads=8)
+        params=oracle.default_params(N, tol_polish=1e-4), prev_status=d["prev_status"], threads=8, passes=pas)
     assert (st == 0).all()
     np.testing.assert_array_equal(out["status"].cpu().numpy(), st)
     np.testing.assert_array_equal(out["iters"].cpu().numpy(), it)
@@ -43,6 +44,8 @@ def test_c5_windows_warm_bitwise(handle, oracle, name):
     np.testing.assert_array_equal(out["vrp"].cpu().numpy(), vrp)
     np.testing.assert_array_equal(out["lam"].cpu().numpy(), lam)
     assert out["polished"].cpu().numpy().all()
+    # the active-set kernels' drop/add passes: these windows run into the anti-cycling passes
+    np.testing.assert_array_equal(out["passes"].cpu().numpy(), pas)
 
 
 @pytest.mark.parametrize("name", ["c5_failed_windows_r03.npz", "c5_hard_windows.npz", "c5_pushed_windows.npz"])
@@ -51,12 +54,16 @@ def test_c5_windows_cold_bitwise(handle, oracle, name):
     dev = {k: torch.from_numpy(np.ascontiguousarray(v)).cuda() for k, v in prob.items()}
     out = handle.dcm_mpc_solve(dev)
     torch.cuda.synchronize()
-    st, xi, vrp, it = oracle.dcm_mpc_solve_batch(prob, threads=8)
+    B = prob["omega"].shape[0]
+    pol, pas = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    st, xi, vrp, it, _ = oracle.dcm_mpc_solve_batch_warm(prob, threads=8, polished=pol, passes=pas)
     assert (st == 0).all()
     np.testing.assert_array_equal(out["status"].cpu().numpy(), st)
     np.testing.assert_array_equal(out["iters"].cpu().numpy(), it)
     np.testing.assert_array_equal(out["xi"].cpu().numpy(), xi)
     np.testing.assert_array_equal(out["vrp"].cpu().numpy(), vrp)
+    np.testing.assert_array_equal(out["polished"].cpu().numpy(), pol)
+    np.testing.assert_array_equal(out["passes"].cpu().numpy(), pas)
 
 
 def test_c5_device_window_r05_bitwise(handle, oracle):
@@ -74,11 +81,12 @@ def test_c5_device_window_r05_bitwise(handle, oracle):
                 shift=1, floor=1e-3, status=torch.from_numpy(d["prev_status"]).cuda())
     out = handle.dcm_mpc_solve(dev, prm, warm=warm, lambda_out=True)
     torch.cuda.synchronize()
+    pas = np.zeros(B, np.int32)
     st, xi, vrp, it, lam = oracle.dcm_mpc_solve_batch_warm(
         prob, vrp_ws=d["vrp_ws"], lam_ws=d["lam_ws"], shift=1, floor=1e-3,
         params=oracle.default_params(N, tol_polish=1e-4, max_iter=100), prev_status=d["prev_status"],
-        threads=1, device_batch=16384)
+        threads=1, device_batch=16384, passes=pas)
     assert (st == 0).all() and (it == 22).all()
-    for k, ref in (("status", st), ("iters", it), ("xi", xi), ("vrp", vrp), ("lam", lam)):
+    for k, ref in (("status", st), ("iters", it), ("xi", xi), ("vrp", vrp), ("lam", lam), ("passes", pas)):
         np.testing.assert_array_equal(out[k].cpu().numpy(), ref, err_msg=k)
     assert out["polished"].cpu().numpy().all()
