@@ -1,6 +1,7 @@
 // fb_common.h -- the device code the floating-base kernel files share (fb_dynamics.hip: dynamics,
 // Euler integration, centre of mass, frame states; fb_ik.hip: whole-body inverse kinematics): the
-// LDS layout, the model, the tree topology and the forward kinematics.
+// LDS layout, the model, the tree topology, the forward kinematics and the staging of a system's
+// state.
 #pragma once
 
 #include "blf_internal.h"
@@ -526,6 +527,31 @@ __device__ __forceinline__ void frame_state(const double* k, const double* fp, d
     for (int a = 0; a < 3; ++a) {
         tw[a] = k[kV + a] + t1[a];
         tw[3 + a] = k[kW + a];
+    }
+}
+
+// A system's state in LDS (Smem st), the layout every kernel hands fbd_kinematics:
+//   bv 6 | jv n | bp 3 | bR 9 | jp n [| dR 9: the rotation's rate, in the kernels that integrate]
+// load_state stages system q's from HBM, the half's lanes striding over the elements (the caller
+// fences).  Used by the kernels that compile to the same assembly with it (fb_dcm_kernel,
+// fb_frame_state_kernel); fbd_dynamics_kernel, fbd_euler_kernel and fb_ik_kernel keep this loop
+// as their own text: through this function some of their instantiations allocate registers
+// differently and measured 1 to 16 % slower ("Sharing device code between the
+// floating-base kernels").
+template <int HW>
+__device__ __forceinline__ void load_state(const blf_fb_state& st, int64_t q, int n, int lane, double* loc)
+{
+    // (n q once, ahead of the loop: the compiler then shares it with the kernel's own n q, as it
+    // did when this loop stood in the kernels -- identical assembly, tools/isa_same.sh)
+    const int64_t nq = (int64_t)n * q;
+    for (int i = lane; i < 18 + 2 * n; i += HW) {
+        double v;
+        if (i < 6) v = st.base_vel[6 * q + i];
+        else if (i < 6 + n) v = st.joint_vel[nq + (i - 6)];
+        else if (i < 9 + n) v = st.base_pos[3 * q + (i - 6 - n)];
+        else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else v = st.joint_pos[nq + (i - 18 - n)];
+        loc[i] = v;
     }
 }
 

@@ -799,16 +799,8 @@ __global__ __launch_bounds__(64) void fb_dcm_kernel(Model m, blf_fb_state st, co
     const Smem S(smem, n, 0, true);   // kinematics only: the compact (articulated-body) layout
     const int64_t q = blockIdx.x;
     const int lane = threadIdx.x;
-    double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n
-    for (int i = lane; i < 18 + 2 * n; i += kWave) {
-        double v;
-        if (i < 6) v = st.base_vel[6 * q + i];
-        else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
-        else if (i < 9 + n) v = st.base_pos[3 * q + (i - 6 - n)];
-        else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
-        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
-        loc[i] = v;
-    }
+    double* loc = S.st();
+    load_state<kWave>(st, q, n, lane, loc);
     wave_sync();
     const Topo T = build_topo<kWave>(m, S);
     fbd_kinematics<kWave, PRI>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n, T);
@@ -856,16 +848,8 @@ __global__ __launch_bounds__(64) void fb_frame_state_kernel(Model m, blf_fb_stat
     const Smem S(smem, n, 0, true);   // kinematics only: the compact (articulated-body) layout
     const int64_t q = blockIdx.x;
     const int lane = threadIdx.x;
-    double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n
-    for (int i = lane; i < 18 + 2 * n; i += kWave) {
-        double v;
-        if (i < 6) v = st.base_vel[6 * q + i];
-        else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
-        else if (i < 9 + n) v = st.base_pos[3 * q + (i - 6 - n)];
-        else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
-        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
-        loc[i] = v;
-    }
+    double* loc = S.st();
+    load_state<kWave>(st, q, n, lane, loc);
     wave_sync();
     const Topo T = build_topo<kWave>(m, S);
     fbd_kinematics<kWave, PRI>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n, T);
