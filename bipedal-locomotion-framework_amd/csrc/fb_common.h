@@ -77,7 +77,7 @@ struct Smem {
         o_sax = take(aba ? 0 : kSax * (size_t)NV);
         o_rhs = take((size_t)NV);
         o_cscr = take((size_t)kCs * (C > 0 ? C : 1));
-        o_st = take(18 + 2 * (size_t)n + (size_t)NV + 9);   // Euler state (6 + n + 3 + 9 + n) + acc + dR
+        o_st = take(18 + 2 * (size_t)n + (size_t)NV + 9);   // Euler state (6 + n + 3 + 9 + n) + dR + ref 3 (kRef)
         o_tq = take((size_t)n);                              // the joint impedance's torques
         o_anc = take((size_t)L);
         // fbd_euler_kernel's per-system constants, staged once instead of read from global memory
@@ -296,7 +296,8 @@ __device__ __forceinline__ void crm_add(const double* s, const double* t, double
 //    world pose is folded in at once where the parent is the base, ptr = 0 then means "anchored in
 //    the world") to its link j + 1.  A round composes the record of link ptr -- the segment from
 //    that link's own ptr -- in front: (R, p) <- (R_X R, p_X + R_X p), ptr <- ptr_X.
-//  * Velocities and nu_dot = 0 accelerations as spatial vectors about the world origin: with the
+//  * Velocities and nu_dot = 0 accelerations as spatial vectors about the origin of the frame bp is
+//    given in (the callers' reference point, see load_state): with the
 //    joint motion U_k = qdot_k S_k (S_k = (z_k, o_k x z_k), prismatic (0, z_k)),
 //      V_c = V_B + sum_{k in chain(c)} U_k,   A_c = A_B + V_B x s + sum_{i before k} U_i x U_k,
 //    so the chain element (s, x) = (sum U, sum of the ordered cross products) composes as
@@ -531,25 +532,32 @@ __device__ __forceinline__ void frame_state(const double* k, const double* fp, d
 }
 
 // A system's state in LDS (Smem st), the layout every kernel hands fbd_kinematics:
-//   bv 6 | jv n | bp 3 | bR 9 | jp n [| dR 9: the rotation's rate, in the kernels that integrate]
+//   bv 6 | jv n | bp 3 | bR 9 | jp n [| dR 9: the rotation's rate, in the kernels that integrate] | ref 3
+// The kernels work in the world frame TRANSLATED to the reference point ref = the system's base_pos
+// at kernel entry: the bp slot holds base_pos - ref (zero at entry, exactly) and ref sits at
+// kRef(n).  The spatial quantities of fbd_eval are taken about that point, so their size is the
+// robot's, not its distance from the world origin (fb_dynamics.hip's header says why); whatever
+// reads or writes a world position subtracts or adds ref there.
 // load_state stages system q's from HBM, the half's lanes striding over the elements (the caller
-// fences).  Used by the kernels that compile to the same assembly with it (fb_dcm_kernel,
-// fb_frame_state_kernel); fbd_dynamics_kernel, fbd_euler_kernel and fb_ik_kernel keep this loop
-// as their own text: through this function some of their instantiations allocate registers
-// differently and measured 1 to 16 % slower ("Sharing device code between the
-// floating-base kernels").
+// fences).  Used by fb_dcm_kernel and fb_frame_state_kernel; fbd_dynamics_kernel, fbd_euler_kernel
+// and fb_ik_kernel (which stays in world coordinates: its point Jacobians lose accuracy only
+// linearly with the distance) keep this loop as their own text: through this function some of
+// their instantiations allocate registers differently and measured 1 to 16 % slower (DESIGN.md
+// 3.2, "Sharing device code between the floating-base kernels").
+__host__ __device__ constexpr int kRef(int n) { return 27 + 2 * n; }
+
 template <int HW>
 __device__ __forceinline__ void load_state(const blf_fb_state& st, int64_t q, int n, int lane, double* loc)
 {
-    // (n q once, ahead of the loop: the compiler then shares it with the kernel's own n q, as it
-    // did when this loop stood in the kernels -- identical assembly, tools/isa_same.sh)
     const int64_t nq = (int64_t)n * q;
     for (int i = lane; i < 18 + 2 * n; i += HW) {
         double v;
         if (i < 6) v = st.base_vel[6 * q + i];
         else if (i < 6 + n) v = st.joint_vel[nq + (i - 6)];
-        else if (i < 9 + n) v = st.base_pos[3 * q + (i - 6 - n)];
-        else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else if (i < 9 + n) {
+            loc[kRef(n) + (i - 6 - n)] = st.base_pos[3 * q + (i - 6 - n)];
+            v = 0.0;
+        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
         else v = st.joint_pos[nq + (i - 18 - n)];
         loc[i] = v;
     }

@@ -5,7 +5,17 @@
 //   nu_dot = LLT(M [+ reg]) \ (-h + sum_c J_c^T w_c + [0; tau]).
 // Here the rigid-body terms are computed directly, in the mixed representation (base velocity
 // (dp_B/dt, w_B), world coordinates), for a kinematic tree of revolute joints, with spatial
-// quantities taken about the WORLD ORIGIN, where a composite inertia is a plain sum:
+// quantities taken about ONE FIXED POINT for the whole tree, where a composite inertia is a plain
+// sum.  The point is the system's own base position at kernel entry (the reference point ref,
+// fb_common.h load_state / kRef), not the world origin: nu_dot does not depend on the point, but the
+// arithmetic takes it as differences of terms of size m |c|^2 (Ibar below, the subtree sums and their
+// prefix differences), so about the world origin the rounding error grew with the SQUARE of the
+// robot's distance from it -- measured on an MI355X against the 1e-9 bar: 7e-10 at 8 m, 2e-7 at
+// 128 m, 2e-5 at 1 km, 1e-3 at 8 km (tests/test_gpu_fb_translation.py).  So every position below
+// (c, o_j, p_B, the contact points) is relative to ref: the kernels hold base_pos - ref (zero at
+// entry, exactly; the Euler kernel integrates it and writes ref + it back), subtract ref from the
+// contacts' null-pose positions and add it to the positions fb_frame_state / fb_dcm write.  "The
+// origin" below is that point:
 //   link l:   spatial inertia I_l = (m, h = m c, Ibar = I_c + m(|c|^2 1 - c c^T)) (10 numbers),
 //             spatial force   F_l = (tau_c + c x f, f),  f = m (a_c - g), tau_c = I_c al + w x I_c w
 //             (accelerations at nu_dot = 0);
@@ -64,8 +74,9 @@ extern "C" int blf_debug_fbd_stamps(unsigned long long* out, int reset)
 namespace {
 
 // ---- The articulated-body solve (round 5): nu_dot without M, its factorization or the
-//      substitutions.  With every spatial quantity about the world origin no transform is needed
-//      between a link and its parent, and the accelerations relative to nu_dot = 0 satisfy
+//      substitutions.  With every spatial quantity about one point (the reference point) no
+//      transform is needed between a link and its parent, and the accelerations relative to
+//      nu_dot = 0 satisfy
 //        da_c = da_p + s_j qdd_j   (joint j moves link c = j + 1 from its parent link p),
 //        f_c  = F_c + I_c da_c     (F_c: step 3's force at nu_dot = 0, contacts subtracted),
 //        s_j^T (sum of f over the subtree of c) = tau_j,
@@ -264,7 +275,7 @@ template <int NVMAX, int HW, bool PRI, bool CS, bool ABA>
 __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const double* bv,
                                          const double* jvel, const double* bp, const double* bR,
                                          const double* jp, const double* tau, const Contacts& ct,
-                                         int64_t sys, const double* reg, const Topo& T)
+                                         int64_t sys, const double* reg, const Topo& T, const double* ref)
 {
     static_assert(NVMAX <= HW, "a system's rows must fit its lanes");
     const Half<HW> H;
@@ -304,8 +315,12 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
             for (int a = 0; a < 6; ++a) sc[3 + a] = gw[a];
         } else if constexpr (CS)
             contact_wrench(S.cst() + 25 * ct.C + 4 * c, tw, pose, S.cst() + 13 * ct.C + 12 * c, sc + 3);
-        else
-            contact_wrench(ct.params + 4 * c, tw, pose, ct.null_pose + (sys * ct.C + c) * 12, sc + 3);
+        else {
+            const double* np = ct.null_pose + (sys * ct.C + c) * 12;
+            double ns[12];   // the null pose relative to the reference point
+            for (int a = 0; a < 12; ++a) ns[a] = a < 3 ? np[a] - ref[a] : np[a];
+            contact_wrench(ct.params + 4 * c, tw, pose, ns, sc + 3);
+        }
         sc[0] = pose[0]; sc[1] = pose[1]; sc[2] = pose[2];
         sc[9] = (double)l;
         double xf[3];
@@ -318,7 +333,7 @@ __device__ __forceinline__ bool fbd_eval(const Model& m, const Smem& S, const do
     wave_sync();
     FSTAMP_ADD(3, f_t3);
     // 3. per link: COM, world inertia, Newton-Euler force / moment, and the spatial inertia and
-    //    force about the world origin (lane per link), with the contact wrenches on the link
+    //    force about the reference point (lane per link), with the contact wrenches on the link
     //    (about the origin) subtracted from its force here, once, instead of in every component
     //    group of the subtree sums: 4.070 / 4.078 against 4.198 / 4.200 ms per c5 period
     //    (profiles/r04_fbd_csub_ab.log)
@@ -655,15 +670,17 @@ __global__ __launch_bounds__(64) void fbd_dynamics_kernel(Model m, blf_fb_state 
         double v;
         if (i < 6) v = st.base_vel[6 * q + i];
         else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
-        else if (i < 9 + n) v = st.base_pos[3 * q + (i - 6 - n)];
-        else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else if (i < 9 + n) {   // the reference point; the position relative to it starts at zero
+            loc[kRef(n) + (i - 6 - n)] = st.base_pos[3 * q + (i - 6 - n)];
+            v = 0.0;
+        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
         else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
         loc[i] = v;
     }
     wave_sync();
     const Topo T = build_topo<HW>(m, S);
     const bool ok = fbd_eval<NVMAX, HW, PRI, false, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
-                                                         tau + (int64_t)n * q, ct, q, reg, T);
+                                                         tau + (int64_t)n * q, ct, q, reg, T, loc + kRef(n));
     if (!active) return;
     const double nan = __builtin_nan("");
     for (int c = lane; c < NV; c += HW) {
@@ -717,8 +734,10 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m
         double v;
         if (i < 6) v = st.base_vel[6 * q + i];
         else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
-        else if (i < 9 + n) v = st.base_pos[3 * q + (i - 6 - n)];
-        else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else if (i < 9 + n) {   // the reference point; the position relative to it starts at zero
+            loc[kRef(n) + (i - 6 - n)] = st.base_pos[3 * q + (i - 6 - n)];
+            v = 0.0;
+        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
         else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
         loc[i] = v;
     }
@@ -728,7 +747,11 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m
             double v;
             if (i < C) v = (double)m.flink[ct.frame[i]];
             else if (i < 13 * C) v = m.fpose[12 * ct.frame[(i - C) / 12] + (i - C) % 12];
-            else if (i < 25 * C) v = ct.null_pose[(q * C) * 12 + (i - 13 * C)];
+            else if (i < 25 * C) {   // null poses, their positions relative to the reference point
+                const int e = (i - 13 * C) % 12;
+                v = ct.null_pose[(q * C) * 12 + (i - 13 * C)];
+                if (e < 3) v = v - st.base_pos[3 * q + e];
+            }
             else v = ct.params[i - 25 * C];
             S.cst()[i] = v;
         }
@@ -755,7 +778,7 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m
             tq = S.tq();
         }
         ok = fbd_eval<NVMAX, HW, PRI, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
-                                                tq, ct, q, reg, T) && ok;
+                                                tq, ct, q, reg, T, loc + kRef(n)) && ok;
         if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, loc + 3, dR);
         wave_sync();
         // every element moves by its derivative at the start of the step (ForwardEuler.tpp:37-45):
@@ -776,7 +799,7 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m
             const double v = ok ? loc[i] : nan;
             if (i < 6) st.base_vel[6 * q + i] = v;
             else if (i < 6 + n) st.joint_vel[(int64_t)n * q + (i - 6)] = v;
-            else if (i < 9 + n) st.base_pos[3 * q + (i - 6 - n)] = v;
+            else if (i < 9 + n) st.base_pos[3 * q + (i - 6 - n)] = loc[kRef(n) + (i - 6 - n)] + v;
             else if (i < 18 + n) st.base_rot[9 * q + (i - 9 - n)] = v;
             else st.joint_pos[(int64_t)n * q + (i - 18 - n)] = v;
         }
@@ -825,6 +848,7 @@ __global__ __launch_bounds__(64) void fb_dcm_kernel(Model m, blf_fb_state st, co
     if (lane == 0) {
         double o[6];
         for (int i = 0; i < 6; ++i) o[i] = a[i] / a[6];
+        for (int i = 0; i < 3; ++i) o[i] = loc[kRef(n) + i] + o[i];   // back to world coordinates
         for (int i = 0; i < 6; ++i) com[6 * q + i] = o[i];
         if (xi) {
             const double w0 = omega0[q * ostride];
@@ -859,6 +883,7 @@ __global__ __launch_bounds__(64) void fb_frame_state_kernel(Model m, blf_fb_stat
         double p[12], tw[6];
         if (f >= 0 && f < m.F) {
             frame_state(S.link() + S.lrec * m.flink[f], m.fpose + 12 * f, p, tw);
+            for (int a = 0; a < 3; ++a) p[a] = loc[kRef(n) + a] + p[a];   // back to world coordinates
         } else {   // a frame index outside [0, nframes): NaN, never an out-of-bounds read
             for (int a = 0; a < 12; ++a) p[a] = __builtin_nan("");
             for (int a = 0; a < 6; ++a) tw[a] = __builtin_nan("");

@@ -66,11 +66,13 @@ def kkt_solve(prob, i, active, q=(1e2, 1e2), rw=(1.0, 1.0), pw=(1e3, 1e3), dt=0.
     return xi, r, lam, act_idx
 
 
-def certify(prob, i, xi_c, r_c, thresholds=(1e-9, 1e-8, 1e-7, 1e-6, 1e-5)):
+def certify(prob, i, xi_c, r_c, thresholds=(1e-9, 1e-8, 1e-7, 1e-6, 1e-5), feas=1e-12):
     """Dense optimality certificate around a candidate (xi_c, r_c): returns (xi, r) of the exact
     optimum.  The active set is guessed from the candidate's slacks with increasing thresholds;
     a guess is accepted only if the dense solution is primal feasible and every multiplier is
-    nonnegative (then it IS the unique optimum of the strictly convex QP)."""
+    nonnegative (then it IS the unique optimum of the strictly convex QP).  feas: the primal
+    feasibility allowance on a . r - b, for plans far from the origin, where that expression itself
+    rounds at the size of the coordinates."""
     A, bb, m = prob["A"][i], prob["b"][i], prob["nfacets"][i]
     mask = np.arange(A.shape[1])[None, :] < m[:, None]
     viol = np.einsum("kfj,kj->kf", A, r_c) - bb
@@ -78,7 +80,7 @@ def certify(prob, i, xi_c, r_c, thresholds=(1e-9, 1e-8, 1e-7, 1e-6, 1e-5)):
         active = (viol > -thr) & mask
         xi, r, lam, _ = kkt_solve(prob, i, active)
         v2 = (np.einsum("kfj,kj->kf", A, r) - bb)[mask]
-        feasible = v2.size == 0 or v2.max() <= 1e-12
+        feasible = v2.size == 0 or v2.max() <= feas
         # with the sign convention of kkt_solve the inequality multipliers are y >= 0
         if feasible and (lam.size == 0 or lam.min() >= -1e-10):
             return xi, r

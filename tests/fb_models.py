@@ -349,3 +349,165 @@ def reference(cid, kind):
         dyn.append(F.dynamics(cs["model"], cs["states"], i, reg=reg, **kw))
         eul.append(F.euler_integrate(cs["model"], cs["states"], i, T0, T1, DT, reg=reg, **kw))
     return dyn, eul
+
+
+# ---- translations of the world frame ------------------------------------------------------------------
+# tests/test_fb_translation.py (CPU: the references are insensitive to where the origin is) and
+# tests/test_gpu_fb_translation.py (the kernels on the shifted inputs against the references on the
+# unshifted ones) share these.  Positions are first rounded to a grid of 2^-bits m, so adding a power-
+# of-two shift is exact and the shifted problem is the same physical problem bit for bit.
+SHIFTS = (3, 7, 10, 13)   # 8 m, 128 m, 1 km, 8 km from the origin
+
+
+def on_grid(a, bits=20):
+    """a rounded to multiples of 2^-bits."""
+    s = float(2 ** bits)
+    return np.round(np.asarray(a, dtype=np.float64) * s) / s
+
+
+def shift_vec(k):
+    return np.array([2.0 ** k, -(2.0 ** k), 2.0 ** (k - 1)])
+
+
+def _shifted(a, d):
+    """a + d on the leading len(d) components of the last axis, asserted exact."""
+    m = len(d)
+    out = np.array(a, dtype=np.float64, copy=True)
+    out[..., :m] = out[..., :m] + d
+    assert np.array_equal(out[..., :m] - d, np.asarray(a)[..., :m]), "the shift must be exact"
+    return out
+
+
+def shift_case(states, contacts, k):
+    """((states, contacts) with base_pos and null_pose[..., :3] on the grid, the same shifted by
+    shift_vec(k)); contacts may be None."""
+    d = shift_vec(k)
+    g_st = dict(states, base_pos=on_grid(states["base_pos"]))
+    s_st = dict(g_st, base_pos=_shifted(g_st["base_pos"], d))
+    g_ct = s_ct = None
+    if contacts is not None:
+        null = np.array(contacts["null_pose"], dtype=np.float64, copy=True)
+        null[..., :3] = on_grid(null[..., :3])
+        g_ct = dict(contacts, null_pose=null)
+        s_ct = dict(contacts, null_pose=_shifted(null, d))
+    return (g_st, g_ct), (s_st, s_ct)
+
+
+def shift_ik(states, tasks, k):
+    """The same for an IK case: base_pos, se3_pose[..., :3] and com_pos."""
+    d = shift_vec(k)
+    g_st = dict(states, base_pos=on_grid(states["base_pos"]))
+    s_st = dict(g_st, base_pos=_shifted(g_st["base_pos"], d))
+    g_tk, s_tk = dict(tasks), dict(tasks)
+    pose = np.array(tasks["se3_pose"], dtype=np.float64, copy=True)
+    pose[..., :3] = on_grid(pose[..., :3])
+    g_tk["se3_pose"], s_tk["se3_pose"] = pose, _shifted(pose, d)
+    if tasks.get("com_pos") is not None:
+        g_tk["com_pos"] = on_grid(tasks["com_pos"])
+        s_tk["com_pos"] = _shifted(g_tk["com_pos"], d)
+    return (g_st, g_tk), (s_st, s_tk)
+
+
+QP_SHIFTS = (10, 13)
+QP_KEYS = ("xi_init", "xi_ref", "vrp_ref", "corners")
+
+
+def shift_plan(prob, k):
+    """(the DCM-MPC batch `prob` with xi_init, xi_ref, vrp_ref and corners rounded to 2^-24 m, the same
+    shifted by (2^k, -2^(k-1)))."""
+    d = np.array([2.0 ** k, -(2.0 ** (k - 1))])
+    g = dict(prob)
+    for key in QP_KEYS:
+        g[key] = np.ascontiguousarray(on_grid(prob[key], 24))
+    s = dict(g)
+    for key in QP_KEYS:
+        s[key] = np.ascontiguousarray(_shifted(g[key], d))
+    return g, s
+
+
+def base_pos_allowance(k, steps):
+    """|(base_pos shifted back) - reference| after `steps` Euler steps: one rounding of a coordinate of
+    size <= 2^(k+1) per step and per side, and the 1e-9 of the comparison itself."""
+    return steps * 2.0 ** (k - 51) + 1e-9
+
+
+def position_allowance(k, tol=1e-9):
+    """A position written in shifted world coordinates and shifted back: 4 roundings at 2^(k-52)."""
+    return 4 * 2.0 ** (k - 52) + tol
+
+
+# (case, regularisation kind) of the translation tests: "none" the articulated-body solve, "reg" /
+# "zero" the mass-matrix path with mass_reg = REG I / zeros.  "humanoid24": robot.humanoid24 with
+# two sole contacts whose null poses lie N(0, 0.01) m from the origin, identity rotations.
+TRANSLATION_RUNS = [("humanoid24", k) for k in ("none", "zero", "reg")]
+for _c, _kinds in (("rand26-c8", "nrz"), ("rand26-c8-dfs", "rz"), ("rand48-c8mixed", "nrz"),
+                   ("rand48-c8mixed-dfs", "rz"), ("chain48-c2", "nrz"), ("star48-c2", "rz"),
+                   ("pri-rand48-c2", "nrz"), ("n1-c2", "rz")):
+    TRANSLATION_RUNS += [(_c, dict(n="none", r="reg", z="zero")[_k]) for _k in _kinds]
+TRANSLATION_KIN_CASES = ("chain48", "bfs27")
+TRANSLATION_IK_CASES = ("rand24-k2com", "chain27-k2com", "rand48-k4com-dfs", "chain48-k2com-far",
+                        "pri-rand48-k2", "star48-k0com")
+IK_STEPS, IK_DT = 3, 0.01
+EULER_STEPS = 3   # of (T0, T1, DT)
+
+
+@functools.lru_cache(maxsize=None)
+def translation_case(cid):
+    """build_case(cid), or the humanoid with its two sole contacts (B = 5 and a sentinel row)."""
+    if cid != "humanoid24":
+        return build_case(cid)
+    model, B = robot.humanoid24(), 5
+    states = robot.random_states(model, B + 1, seed=21)
+    null = np.zeros((B + 1, 2, 12))
+    null[:, :, :3] = np.random.default_rng(0).normal(size=(B + 1, 2, 3)) * 0.01
+    null[:, :, 3:] = np.eye(3).reshape(-1)
+    ct = dict(frame=np.array([0, 1], dtype=np.int32), params=np.array([[0.12, 0.09, 3.0e4, 300.0]] * 2),
+              null_pose=null, law=None, wrench=None)
+    return dict(model=model, B=B, states=states, contacts=ct)
+
+
+def oracle_run(model, B, states, contacts, kind):
+    """F.dynamics and the three-step F.euler_integrate of systems 0 .. B - 1 (reference()'s pair)."""
+    reg = reg_of(model, "reg") if kind == "reg" else None
+    dyn, eul = [], []
+    for i in range(B):
+        kw = oracle_kw(contacts, i)
+        dyn.append(F.dynamics(model, states, i, reg=reg, **kw))
+        eul.append(F.euler_integrate(model, states, i, T0, T1, DT, reg=reg, **kw))
+    return dyn, eul
+
+
+@functools.lru_cache(maxsize=None)
+def translation_reference(cid, kind):
+    """oracle_run on the case's grid-rounded, UNSHIFTED inputs (kind "zero" is "none"'s), once per
+    (case, kind) and shared; the rounding does not depend on the shift."""
+    cs = translation_case(cid)
+    (st, ct), _ = shift_case(cs["states"], cs["contacts"], 0)
+    return oracle_run(cs["model"], cs["B"], st, ct, "reg" if kind == "reg" else "none")
+
+
+@functools.lru_cache(maxsize=None)
+def impedance_case(stiff=True):
+    """The arguments of tests/test_gpu_closed_loop.py::test_fbd_euler_impedance_vs_oracle: six standing
+    humanoids on their soles, 20 Euler steps of 1 ms under the posture law's joint impedance.
+    stiff=False: the soles of tests/test_gpu_fb_dynamics.py (k = 3e4 N/m^3, b = 300) in place of the
+    closed loop's (k = 2e6, b = 2e4), which turn the last place of a world coordinate 8 km out
+    (2^-40 m) into 1.6e-9 of joint velocity in the references themselves."""
+    from blf import closed_loop as DL
+    model, B = robot.humanoid24(), 6
+    st = robot.standing_states(model, B, seed=5)
+    law = robot.posture_law_arrays(model)
+    ct = dict(frame=np.arange(2, dtype=np.int32), params=np.tile(np.asarray(DL.CONTACT_PARAMS if stiff else (0.12, 0.09, 3.0e4, 300.0)), (2, 1)),
+              null_pose=robot.sole_null_poses(model, st), law=None, wrench=None)
+    return dict(model=model, B=B, states=st, contacts=ct, kp=law["kp"], kd=law["kd"],
+                q_ref=np.random.default_rng(3).normal(size=(B, model["n"])) * 0.02,
+                t0=0.0, t1=0.02, dT=0.001, steps=20)
+
+
+def state_errors(got, ref, k, keys):
+    """(worst rel_err over the state keys but base_pos, |(got base_pos - shift_vec(k)) - ref|_inf) of
+    one system: `got` in the shifted world, `ref` in the unshifted one."""
+    worst = max(rel_err(np.asarray(got[key]).reshape(-1), np.asarray(ref[key]).reshape(-1))
+                for key in keys if key != "base_pos")
+    back = float(np.abs((np.asarray(got["base_pos"]) - shift_vec(k)) - ref["base_pos"]).max())
+    return worst, back

@@ -130,3 +130,15 @@ def reference(cid):
     """IK.solve of every robot of the case, computed once and shared: list of (nu, status, H, g)."""
     cs = build_case(cid)
     return [IK.solve(cs["model"], cs["states"], cs["tasks"], i) for i in range(cs["B"])]
+
+
+@functools.lru_cache(maxsize=None)
+def translation_reference(cid):
+    """The reference on the case's grid-rounded, unshifted inputs (fb_models.shift_ik), once per case
+    and shared by the translation tests: (list of IK.solve tuples, list of IK.integrate tuples over
+    fb_models.IK_STEPS steps)."""
+    cs = build_case(cid)
+    (st, tk), _ = FM.shift_ik(cs["states"], cs["tasks"], 0)
+    B = min(cs["B"], 3)
+    return ([IK.solve(cs["model"], st, tk, i) for i in range(B)],
+            [IK.integrate(cs["model"], st, tk, i, FM.IK_STEPS, FM.IK_DT) for i in range(B)])
