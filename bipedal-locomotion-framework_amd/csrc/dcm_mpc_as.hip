@@ -535,7 +535,8 @@ __device__ __forceinline__ void as_solve(const AKnotT<T> (&K)[KPL], const T (&g)
 // Returns false when some factorization pivot is not positive definite (status NUMERICAL; the
 // step is still taken, as in the oracle).
 template <int KPL, int TR, class T>
-__device__ __forceinline__ bool as_lq_step(AKnotT<T> (&K)[KPL], const PT<T>& P, int N, int lane, T xi00, T xi01)
+__device__ __forceinline__ bool as_lq_step_general(AKnotT<T> (&K)[KPL], const PT<T>& P, int N, int lane, T xi00,
+                                                   T xi01)
 {
     T E[KPL][3];
 #pragma unroll
@@ -601,6 +602,371 @@ __device__ __forceinline__ bool as_lq_step(AKnotT<T> (&K)[KPL], const PT<T>& P, 
         }
     }
     return __ballot(!ok) == 0;
+}
+
+// ---- the decoupled LQ step ----
+// With W = 0 and diagonal weights the x and y axes never couple: E[j][1] is a zero, every Riccati
+// element keeps a1 = a2 = g1 = h1 = 0, and P01, h01, m01, m10, G[1], G[2] of the solve are zeros.
+// The functions below are as_riccati, as_scan_backward, as_scan_forward, as_solve and the step
+// above with exactly the operations that do not have one of those zeros as an operand, in the same
+// order, fused forms and scan trees (dcm_qp_common.h: RcD, AfD).  ISO (the instantiated type's
+// weights are equal on both axes) computes the shared values once: one Riccati recursion, one gain
+// per affine element.
+
+// The level's source element of an affine scan, each value moved by mv.
+template <class T, bool ISO, class MV>
+__device__ __forceinline__ AfD<T, ISO> afd_move(const AfD<T, ISO>& a, MV mv)
+{
+    AfD<T, ISO> q;
+    q.g0 = mv(a.g0);
+    if constexpr (ISO) q.g3 = q.g0;
+    else q.g3 = mv(a.g3);
+    q.e0 = mv(a.e0);
+    q.e1 = mv(a.e1);
+    return q;
+}
+
+template <int L, bool FWD, class T, bool ISO>
+__device__ __forceinline__ void afd_level(AfD<T, ISO>& a, int lane)
+{
+    const AfD<T, ISO> q = afd_move(a, [](T v) { return tree_src<L, FWD>(v); });
+    if (tree_has<L, FWD>(lane)) afd_compose(a, q);
+}
+
+// The tree of an affine scan over the lanes' elements (the levels of as_scan_backward / _forward).
+template <int KPL, int TR, bool FWD, class T, bool ISO>
+__device__ __forceinline__ void afd_scan_tree(AfD<T, ISO>& a, int lane)
+{
+    if constexpr (TR == kTreeDpp) {
+        afd_level<0, FWD>(a, lane);
+        afd_level<1, FWD>(a, lane);
+        afd_level<2, FWD>(a, lane);
+        afd_level<3, FWD>(a, lane);
+        afd_level<4, FWD>(a, lane);
+        afd_level<5, FWD>(a, lane);
+    } else {
+        const int ln = opaque(lane);
+        constexpr bool pad = KPL == 2 && TR == kTreePad;
+        {
+            constexpr int C = FWD ? kPrevWrap : pad ? kNextKeep : kNextWrap;
+            const AfD<T, ISO> q = afd_move(a, [](T v) { return dpp1<C>(v); });
+            if (ks_has<pad, FWD>(ln, 1)) afd_compose(a, q);
+        }
+#pragma unroll
+        for (int d = 2; d < kWave; d <<= 1) {
+            const int ad = ks_addr<pad, FWD>(ln, d);
+            const AfD<T, ISO> q = afd_move(a, [ad](T v) { return bperm(ad, v); });
+            if (ks_has<pad, FWD>(ln, d)) afd_compose(a, q);
+        }
+    }
+}
+
+template <int KPL, int TR, class T, bool ISO>
+__device__ __forceinline__ void asd_scan_backward(const AfD<T, ISO> (&el)[KPL], int lane, T (&vn)[KPL][2])
+{
+    AfD<T, ISO> a = el[0];
+    if constexpr (KPL == 2) afd_compose(a, el[1]);   // knot 2l after knot 2l + 1
+    afd_scan_tree<KPL, TR, false>(a, lane);
+    T vb0 = dpp1<kNextWrap>(a.e0), vb1 = dpp1<kNextWrap>(a.e1);
+    if (lane == kWave - 1) {
+        vb0 = T(0);
+        vb1 = T(0);
+    }
+    if constexpr (KPL == 2) {
+        vn[0][0] = fma(el[1].g0, vb0, el[1].e0);   // v_{2l+1}
+        vn[0][1] = fma(ISO ? el[1].g0 : el[1].g3, vb1, el[1].e1);
+        vn[1][0] = vb0;                            // v_{2l+2}
+        vn[1][1] = vb1;
+    } else {
+        vn[0][0] = vb0;
+        vn[0][1] = vb1;
+    }
+}
+
+template <int KPL, int TR, class T, bool ISO>
+__device__ __forceinline__ void asd_scan_forward(const AfD<T, ISO> (&el)[KPL], int lane, T (&x)[KPL][2],
+                                                 T (&xk)[KPL][2])
+{
+    constexpr int L = KPL - 1;   // the lane's last knot
+    AfD<T, ISO> a = el[L];
+    if constexpr (KPL == 2) afd_compose(a, el[0]);   // knot 2l + 1 after knot 2l
+    afd_scan_tree<KPL, TR, true>(a, lane);
+    T xb0 = dpp1<kPrevWrap>(a.e0), xb1 = dpp1<kPrevWrap>(a.e1);
+    if (lane == 0) {
+        xb0 = T(0);
+        xb1 = T(0);
+    }
+    xk[0][0] = xb0;
+    xk[0][1] = xb1;
+    if constexpr (KPL == 2) {
+        const T x10 = fma(el[0].g0, xb0, el[0].e0);   // x_{2l+1}
+        const T x11 = fma(ISO ? el[0].g0 : el[0].g3, xb1, el[0].e1);
+        x[0][0] = x10;
+        x[0][1] = x11;
+        xk[1][0] = x10;
+        xk[1][1] = x11;
+    }
+    x[L][0] = a.e0;
+    x[L][1] = a.e1;
+}
+
+template <class T>
+__device__ __forceinline__ void rcd_knot(RcD<T>& e, bool own, T al, const T (&E)[2], const PT<T>& P)
+{
+    if (own) {
+        e.a0 = al; e.a3 = al;
+        e.g0 = E[0]; e.g2 = E[1];
+        e.h0 = P.Qw0; e.h2 = P.Qw1;
+    } else {
+        e.a0 = T(1); e.a3 = T(1);
+        e.g0 = e.g2 = T(0);
+        e.h0 = e.h2 = T(0);
+    }
+}
+
+template <class T, bool ISO, class MV>
+__device__ __forceinline__ RcD<T> rcd_move(const RcD<T>& e, MV mv)
+{
+    RcD<T> q;
+    q.a0 = mv(e.a0);
+    q.g0 = mv(e.g0);
+    q.h0 = mv(e.h0);
+    if constexpr (ISO) {
+        q.a3 = q.a0;
+        q.g2 = q.g0;
+        q.h2 = q.h0;
+    } else {
+        q.a3 = mv(e.a3);
+        q.g2 = mv(e.g2);
+        q.h2 = mv(e.h2);
+    }
+    return q;
+}
+
+template <int L, bool ISO, class T>
+__device__ __forceinline__ void rcd_tree(RcD<T>& e, bool& ok, int lane)
+{
+    const RcD<T> q = rcd_move<T, ISO>(e, [](T v) { return tree_bwd<L>(v); });
+    if (tree_has<L, false>(lane)) ok = rcd_combine<ISO>(e, q) && ok;
+}
+
+// as_riccati for diagonal elements (E = (E00, E11)); Pk = (P00, P11)_{k+1} of every slot
+template <int KPL, int TR, bool ISO, class T>
+__device__ __forceinline__ bool asd_riccati(const AKnotT<T> (&K)[KPL], const PT<T>& P, const T (&E)[KPL][2], int N,
+                                            int lane, T (&Pk)[KPL][2])
+{
+    bool ok = true;
+    RcD<T> e;
+    rcd_knot(e, KPL * lane < N, K[0].al, E[0], P);
+    if constexpr (KPL == 2) {
+        RcD<T> e1;
+        rcd_knot(e1, KPL * lane + 1 < N, K[1].al, E[1], P);
+        ok = rcd_combine<ISO>(e, e1) && ok;
+    }
+    if constexpr (TR == kTreeDpp) {
+        rcd_tree<0, ISO>(e, ok, lane);
+        rcd_tree<1, ISO>(e, ok, lane);
+        rcd_tree<2, ISO>(e, ok, lane);
+        rcd_tree<3, ISO>(e, ok, lane);
+        rcd_tree<4, ISO>(e, ok, lane);
+        rcd_tree<5, ISO>(e, ok, lane);
+    } else {
+        const int ln = opaque(lane);
+        constexpr bool pad = KPL == 2 && TR == kTreePad;
+        {   // d = 1 (DPP; as_pad: lane 63 keeps its own identity)
+            constexpr int C = pad ? kNextKeep : kNextWrap;
+            const RcD<T> q = rcd_move<T, ISO>(e, [](T v) { return dpp1<C>(v); });
+            if (ks_has<pad, false>(ln, 1)) ok = rcd_combine<ISO>(e, q) && ok;
+        }
+#pragma unroll
+        for (int d = 2; d < kWave; d <<= 1) {
+            const int ad = ks_addr<pad, false>(ln, d);
+            const RcD<T> q = rcd_move<T, ISO>(e, [ad](T v) { return bperm(ad, v); });
+            if (ks_has<pad, false>(ln, d)) ok = rcd_combine<ISO>(e, q) && ok;
+        }
+    }
+    // P at this lane's first knot; the next lane's (terminal past the last lane)
+    T P00, P11;
+    ok = rcd_apply<ISO>(e, P.Pw0, P.Pw1, P00, P11) && ok;
+    T Pn00 = dpp1<kNextWrap>(P00), Pn11 = ISO ? Pn00 : dpp1<kNextWrap>(P11);
+    if (lane == kWave - 1) {
+        Pn00 = P.Pw0;
+        Pn11 = P.Pw1;
+    }
+    constexpr int L = KPL - 1;
+    Pk[L][0] = Pn00;
+    Pk[L][1] = Pn11;
+    if constexpr (KPL == 2) {   // P_{2l+1} = f_{2l+1}(P_{2l+2}), the first knot's P_{k+1}
+        RcD<T> e1;
+        rcd_knot(e1, KPL * lane + 1 < N, K[1].al, E[1], P);
+        ok = rcd_apply<ISO>(e1, Pn00, Pn11, Pk[0][0], Pk[0][1]) && ok;
+    }
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        if (KPL * lane + j == N - 1) {
+            Pk[j][0] = P.Pw0;
+            Pk[j][1] = P.Pw1;
+        }
+    }
+    return ok;
+}
+
+// as_solve for diagonal P = (Pk[0], Pk[1]) and h = (hk[0], hk[1]); the costates vn are not returned
+template <int KPL, int TR, bool ISO, class T>
+__device__ __forceinline__ void asd_solve(const AKnotT<T> (&K)[KPL], const T (&Pk)[KPL][2], const T (&hk)[KPL][2],
+                                          const T (&g)[KPL][2], int N, int lane, T (&dr)[KPL][2], T (&dx)[KPL][2])
+{
+    AfD<T, ISO> el[KPL];
+    T y[KPL][2], m[KPL][2], vn[KPL][2];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        const AKnotT<T>& Kj = K[j];
+        m[j][0] = Pk[j][0] * hk[j][0];
+        m[j][1] = ISO ? m[j][0] : Pk[j][1] * hk[j][1];
+        el[j].g0 = el[j].g3 = el[j].e0 = el[j].e1 = T(0);
+        y[j][0] = y[j][1] = T(0);
+        if (KPL * lane + j < N) {
+            const T b2 = Kj.be * Kj.be;
+            const T ab = Kj.al * Kj.be;
+            y[j][0] = fma(Pk[j][0], Kj.d0, Kj.qx0);
+            y[j][1] = fma(Pk[j][1], Kj.d1, Kj.qx1);
+            const T Mg0 = m[j][0] * g[j][0];
+            const T Mg1 = m[j][1] * g[j][1];
+            el[j].g0 = Kj.al * fma(-b2, m[j][0], T(1));
+            el[j].g3 = ISO ? el[j].g0 : Kj.al * fma(-b2, m[j][1], T(1));
+            el[j].e0 = fma(el[j].g0, y[j][0], ab * Mg0);
+            el[j].e1 = fma(el[j].g3, y[j][1], ab * Mg1);
+        }
+    }
+    asd_scan_backward<KPL, TR, T, ISO>(el, lane, vn);
+    T k[KPL][2];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        k[j][0] = k[j][1] = el[j].e0 = el[j].e1 = T(0);   // the forward scan's gains are the backward's
+        if (KPL * lane + j < N) {
+            const AKnotT<T>& Kj = K[j];
+            const T t0 = y[j][0] + vn[j][0];
+            const T t1 = y[j][1] + vn[j][1];
+            const T hu0 = fma(-Kj.be, t0, g[j][0]);
+            const T hu1 = fma(-Kj.be, t1, g[j][1]);
+            k[j][0] = -(hk[j][0] * hu0);
+            k[j][1] = -(hk[j][1] * hu1);
+            el[j].e0 = fma(-Kj.be, k[j][0], Kj.d0);
+            el[j].e1 = fma(-Kj.be, k[j][1], Kj.d1);
+        }
+    }
+    T xk[KPL][2];
+    asd_scan_forward<KPL, TR, T, ISO>(el, lane, dx, xk);
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        const T ab = K[j].al * K[j].be;
+        dr[j][0] = fma(ab, m[j][0] * xk[j][0], k[j][0]);
+        dr[j][1] = fma(ab, m[j][1] * xk[j][1], k[j][1]);
+    }
+}
+
+// Zero, infinite or not a number (v_cmp_class: +-0, +-inf, sNaN, qNaN).
+__device__ __forceinline__ bool zero_or_nonfinite(float v) { return __builtin_amdgcn_classf(v, 0x267); }
+__device__ __forceinline__ bool zero_or_nonfinite(double v) { return __builtin_amdgcn_class(v, 0x267); }
+
+// The decoupled step.  Leaves r and x of the step in K; K.P and K.h are not written (every caller's
+// next reader, as_passes or the outputs, takes them from its own sweep or not at all).  Returns
+// false when the step is not known to be the general step's bit for bit, and the caller then takes
+// the general step from the saved point:
+//   * while every intermediate is finite, a dropped term is an exact zero added to a kept term, so
+//     each kept operation rounds as in the general form, unless the kept term is itself an exact
+//     zero, whose sign the dropped zero can change.  A sign of zero changes no comparison and no
+//     sum or product with a non-zero value; it reaches the result only as a result that is itself
+//     a zero, or through a division by it, and the divisors are the determinants `ok` tests;
+//   * a non-finite intermediate (where the dropped 0 x inf would be a NaN) makes every value
+//     computed from it non-finite, except through those same divisions;
+// so a step whose `ok` holds on every lane and whose r and x are all finite and non-zero is the
+// general step's.  (A reference that is exactly zero on one axis therefore costs the general step
+// as well; the result is the same.)
+template <int KPL, int TR, bool ISO, class T>
+__device__ __forceinline__ bool asd_lq_step(AKnotT<T> (&K)[KPL], const PT<T>& P, int N, int lane, T xi00, T xi01)
+{
+    T E[KPL][2];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        E[j][0] = E[j][1] = T(0);
+        if (KPL * lane + j < N) {
+            const T b2 = K[j].be * K[j].be;
+            const T W00 = T(0), W11 = T(0), dW = T(0);
+            const T detRW = fma(P.Rw0, P.Rw1, FD2(P.Rw1, W00, P.Rw0, W11)) + dW;
+            const T ie = b2 / detRW;
+            E[j][0] = (P.Rw1 + W11) * ie;
+            E[j][1] = ISO ? E[j][0] : (P.Rw0 + W00) * ie;
+        }
+    }
+    T Pk[KPL][2], hk[KPL][2];
+    bool ok = asd_riccati<KPL, TR, ISO, T>(K, P, E, N, lane, Pk);
+    {
+        T xk[KPL][2];
+        as_xi_prev<KPL, T>(K, lane, xi00, xi01, xk);
+#pragma unroll
+        for (int j = 0; j < KPL; ++j) {
+            const int k = KPL * lane + j;
+            if (k < N) as_residuals(K[j], P, k == N - 1, xk[j][0], xk[j][1]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        hk[j][0] = hk[j][1] = T(0);
+        if (KPL * lane + j < N) {
+            const T b2 = K[j].be * K[j].be;
+            const T B00 = fma(b2, Pk[j][0], P.Rw0);
+            const T B11 = ISO ? B00 : fma(b2, Pk[j][1], P.Rw1);
+            const T det = B00 * B11;
+            if (!(det > T(0)) || __builtin_isinf(det)) ok = false;
+            const T idet = T(1) / det;
+            hk[j][0] = B11 * idet;
+            hk[j][1] = ISO ? hk[j][0] : B00 * idet;
+        }
+    }
+    T g[KPL][2], dr[KPL][2], dx[KPL][2];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        g[j][0] = K[j].rh0;
+        g[j][1] = K[j].rh1;
+    }
+    asd_solve<KPL, TR, ISO, T>(K, Pk, hk, g, N, lane, dr, dx);
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        if (KPL * lane + j < N) {
+            K[j].r0 = K[j].r0 + dr[j][0];
+            K[j].r1 = K[j].r1 + dr[j][1];
+            K[j].x0 = K[j].x0 + dx[j][0];
+            K[j].x1 = K[j].x1 + dx[j][1];
+            if (zero_or_nonfinite(K[j].r0) || zero_or_nonfinite(K[j].r1) || zero_or_nonfinite(K[j].x0) ||
+                zero_or_nonfinite(K[j].x1))
+                ok = false;
+        }
+    }
+    return __ballot(!ok) == 0;
+}
+
+// The LQ step of the kernels: the decoupled form (one axis when the instantiated type's weights
+// are the same on both: a kernel-uniform test; two doubles can differ and round to one float, so
+// the float step tests the float weights), and the general form from the same point where the
+// decoupled one does not vouch for its result (asd_lq_step).
+template <int KPL, int TR, class T>
+__device__ __forceinline__ bool as_lq_step(AKnotT<T> (&K)[KPL], const PT<T>& P, int N, int lane, T xi00, T xi01)
+{
+    T sv[KPL][4];
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        sv[j][0] = K[j].r0; sv[j][1] = K[j].r1; sv[j][2] = K[j].x0; sv[j][3] = K[j].x1;
+    }
+    const bool iso = P.Qw0 == P.Qw1 && P.Rw0 == P.Rw1 && P.Pw0 == P.Pw1;
+    const bool same = iso ? asd_lq_step<KPL, TR, true, T>(K, P, N, lane, xi00, xi01)
+                          : asd_lq_step<KPL, TR, false, T>(K, P, N, lane, xi00, xi01);
+    if (same) return true;
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        K[j].r0 = sv[j][0]; K[j].r1 = sv[j][1]; K[j].x0 = sv[j][2]; K[j].x1 = sv[j][3];
+    }
+    return as_lq_step_general<KPL, TR, T>(K, P, N, lane, xi00, xi01);
 }
 
 // More than two candidate lines in a pass: the first pair (i < j in facet order) whose vertex

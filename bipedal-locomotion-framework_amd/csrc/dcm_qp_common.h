@@ -463,6 +463,109 @@ __device__ __forceinline__ bool rc_apply(const RcT<T>& e, T P00, T P01, T P11, T
     return ok;
 }
 
+// ---- the decoupled forms (the LQ step of dcm_mpc_as.hip: no facet terms, diagonal weights) ----
+// Without facet terms every G_k, H_k and A_k is diagonal, and the composition keeps it so: a1, a2,
+// g1 and h1 of every element are exact zeros, and so is every T01, T10, U01, ... above.  RcD holds
+// the six other values; rcd_combine / rcd_apply perform the operations of rc_combine / rc_apply
+// whose operands are not among those zeros, in the same order and the same fused forms.  A dropped
+// term is (zero x finite) added by an fma or an add to a kept term, so while every value is finite
+// the kept operations round as they do above; the result can differ only in the sign of an exact
+// zero (a kept product with a zero factor), which no later operation turns into anything but the
+// sign of another zero or, as a divisor, an infinity the `ok` tests report.
+// ISO: the weights of the two axes are equal, so the two axes' values are the same numbers
+// (T00 == T11, a0 == a3, ... bit for bit: every x operation has the y operation's operands) and
+// the x axis alone is computed; a3, g2, h2 are then copies.
+template <class T>
+struct RcD {
+    T a0, a3, g0, g2, h0, h2;
+};
+
+template <bool ISO, class T>
+__device__ __forceinline__ bool rcd_combine(RcD<T>& e, const RcD<T>& q)
+{
+    const T one = T(1);
+    const T T00 = fma(e.g0, q.h0, one);
+    const T T11 = ISO ? T00 : fma(e.g2, q.h2, one);
+    const T detT = T00 * T11;
+    const bool ok = (detT > T(0)) && !__builtin_isinf(detT);
+    const T it = one / detT;
+    RcD<T> r;
+    {
+        const T Up00 = T11 * e.a0;
+        const T Vp00 = q.a0 * T11;
+        const T Xp00 = Vp00 * e.g0;
+        const T Y00 = q.h0 * e.a0;
+        const T gp0 = Xp00 * q.a0;
+        const T U00 = Up00 * it;
+        r.a0 = q.a0 * U00;
+        r.h0 = fma(U00, Y00, e.h0);
+        r.g0 = fma(gp0, it, q.g0);
+    }
+    if constexpr (ISO) {
+        r.a3 = r.a0;
+        r.h2 = r.h0;
+        r.g2 = r.g0;
+    } else {
+        const T Up11 = T00 * e.a3;
+        const T Vp11 = q.a3 * T00;
+        const T Xp11 = Vp11 * e.g2;
+        const T Y11 = q.h2 * e.a3;
+        const T gp2 = Xp11 * q.a3;
+        const T U11 = Up11 * it;
+        r.a3 = q.a3 * U11;
+        r.h2 = fma(U11, Y11, e.h2);
+        r.g2 = fma(gp2, it, q.g2);
+    }
+    e = r;
+    return ok;
+}
+
+// rc_apply for a diagonal P (P01 an exact zero; ISO: P00 == P11)
+template <bool ISO, class T>
+__device__ __forceinline__ bool rcd_apply(const RcD<T>& e, T P00, T P11, T& o00, T& o11)
+{
+    const T one = T(1);
+    const T S00 = fma(e.g0, P00, one);
+    const T S11 = ISO ? S00 : fma(e.g2, P11, one);
+    const T detS = S00 * S11;
+    const bool ok = (detS > T(0)) && !__builtin_isinf(detS);
+    const T is = one / detS;
+    const T Wp00 = P00 * S11;
+    const T Zp00 = Wp00 * e.a0;
+    o00 = fma(e.a0 * Zp00, is, e.h0);
+    if constexpr (ISO) {
+        o11 = o00;
+    } else {
+        const T Wp11 = P11 * S00;
+        const T Zp11 = Wp11 * e.a3;
+        o11 = fma(e.a3 * Zp11, is, e.h2);
+    }
+    return ok;
+}
+
+// An element of the affine scans with a diagonal gain (COMPOSE with a1 = a2 = b1 = b2 = 0):
+// gains g0, g3 (ISO: g0 alone, g3 unused) and offsets e0, e1.  afd_compose(a, b): a <- a o b.
+template <class T, bool ISO>
+struct AfD {
+    T g0, g3, e0, e1;
+};
+
+template <class T, bool ISO>
+__device__ __forceinline__ void afd_compose(AfD<T, ISO>& a, const AfD<T, ISO>& b)
+{
+    const T n0 = a.g0 * b.g0;
+    const T m0 = fma(a.g0, b.e0, a.e0);
+    if constexpr (ISO) {
+        a.e1 = fma(a.g0, b.e1, a.e1);
+    } else {
+        const T n3 = a.g3 * b.g3;
+        a.e1 = fma(a.g3, b.e1, a.e1);
+        a.g3 = n3;
+    }
+    a.g0 = n0;
+    a.e0 = m0;
+}
+
 // The phase-indexed input of blf_dcm_mpc_solve_phased: the plan's phase table (blf_phase_table)
 // in place of the window's per-knot arrays, and the window scratch a QP handed to the IPM kernel
 // is expanded into (blf_dcm_mpc_window).
