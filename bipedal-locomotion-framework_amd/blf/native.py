@@ -30,7 +30,8 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_fbk_euler_integrate", "blf_fbd_dynamics", "blf_fbd_euler_integrate",
             "blf_fb_dcm", "blf_dcm_posture_reference", "blf_fbd_euler_integrate_impedance",
             "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance",
-            "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate"]
+            "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate",
+            "blf_fb_ik_solve_hard", "blf_fb_ik_integrate_hard"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -88,7 +89,13 @@ class IkTasks(ctypes.Structure):
                 ("joint_pos", _vp), ("joint_vel", _vp), ("base_damping", _f64)]
 
 
+class IkHard(ctypes.Structure):
+    """blf_ik_hard (include/blf/blf_c.h section 12b)."""
+    _fields_ = [("rows", ctypes.c_uint32), ("reserved", _i32), ("rel_pivot_min", _f64)]
+
+
 IK_OK, IK_NOT_POSITIVE, IK_BAD_INPUT = 0, 1, 2   # per-robot status of fb_ik_solve / fb_ik_integrate
+IK_HARD_DEPENDENT = 3   # with hard rows: a pivot of S failed the rule (section 12b)
 
 SWING_OUTPUTS = ("pose", "twist", "accel", "contact_idx", "in_contact")
 SO3_OUTPUTS = ("rot", "omega", "alpha")
@@ -228,6 +235,11 @@ def lib():
                                       ctypes.POINTER(IkTasks), _i64, _vp, _vp, _vp]
         L.blf_fb_ik_integrate.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
                                           ctypes.POINTER(IkTasks), _i64, _i32, _f64, _vp, _vp, _vp]
+        L.blf_fb_ik_solve_hard.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
+                                           ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard), _i64, _vp, _vp, _vp]
+        L.blf_fb_ik_integrate_hard.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
+                                               ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard), _i64, _i32, _f64,
+                                               _vp, _vp, _vp]
         L.blf_dcm_mpc_flops_per_iter.restype = _f64
         L.blf_set_qp_launch_mode.argtypes = [_i32, _i32]
         for name in EXPORTED:
@@ -1026,10 +1038,30 @@ class Handle:
         tk.c, tk.batch, tk.n = c, B, n
         return tk
 
-    def fb_ik_solve(self, dm, state, tasks, nu=None, status=None, stream=None):
+    @staticmethod
+    def ik_hard(se3=(), com=(False, False, False), rel_pivot_min=0.0):
+        """Build a blf_ik_hard (section 12b): se3 [K][6] bools mark the rows of SE3 task k (linear
+        xyz, angular xyz) that hold exactly, com [3] bools the CoM rows; rel_pivot_min = tau (0: the
+        default 1e-8).  E.g. **robot.standing_ik_hard(model)."""
+        rows = 0
+        se3 = [list(r) for r in se3]
+        if len(se3) > 4 or any(len(r) != 6 for r in se3) or len(com) != 3:
+            raise ValueError("ik_hard: se3 must be [K <= 4][6] bools and com [3] bools")
+        for k, r in enumerate(se3):
+            for a, on in enumerate(r):
+                rows |= int(bool(on)) << (6 * k + a)
+        for a, on in enumerate(com):
+            rows |= int(bool(on)) << (24 + a)
+        h = IkHard()
+        h.rows, h.reserved, h.rel_pivot_min = rows, 0, float(rel_pivot_min)
+        return h
+
+    def fb_ik_solve(self, dm, state, tasks, nu=None, status=None, stream=None, hard=None):
         """blf_fb_ik_solve: nu [B,6+n] = (base mixed twist, joint velocities) minimising the weighted
         task errors at the state's base_pos / base_rot / joint_pos, and the per-robot status [B]
-        int32 (IK_OK / IK_NOT_POSITIVE / IK_BAD_INPUT; status=False: not requested)."""
+        int32 (IK_OK / IK_NOT_POSITIVE / IK_BAD_INPUT; status=False: not requested).
+        hard (an ik_hard()): blf_fb_ik_solve_hard, the marked rows held exactly (status may then be
+        IK_HARD_DEPENDENT); None: today's call."""
         torch = _torch()
         B, n = state["joint_pos"].shape
         dev = state["joint_pos"].device
@@ -1037,15 +1069,22 @@ class Handle:
         if status is None:
             status = torch.empty((B,), dtype=torch.int32, device=dev)
         sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
-        _check(lib().blf_fb_ik_solve(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
-                                     ctypes.byref(tasks.c), B, _ptr(nu, torch.float64, (B, 6 + n), "nu"), sp,
-                                     _stream(stream)))
+        if hard is None:
+            _check(lib().blf_fb_ik_solve(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
+                                         ctypes.byref(tasks.c), B, _ptr(nu, torch.float64, (B, 6 + n), "nu"), sp,
+                                         _stream(stream)))
+        else:
+            _check(lib().blf_fb_ik_solve_hard(self._h, ctypes.byref(dm.c),
+                                              ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c),
+                                              ctypes.byref(hard), B, _ptr(nu, torch.float64, (B, 6 + n), "nu"),
+                                              sp, _stream(stream)))
         return nu, (status if status is not False else None)
 
-    def fb_ik_integrate(self, dm, state, tasks, steps, dT, nu=None, status=None, stream=None):
+    def fb_ik_integrate(self, dm, state, tasks, steps, dT, nu=None, status=None, stream=None, hard=None):
         """blf_fb_ik_integrate: `steps` x (solve, one Euler step of dT) in one launch, in place on
         `state` (base_vel / joint_vel receive the last step's nu).  nu / status as fb_ik_solve;
-        False: not requested.  Returns (state, nu, status)."""
+        False: not requested.  hard as fb_ik_solve (blf_fb_ik_integrate_hard).  Returns (state, nu,
+        status)."""
         torch = _torch()
         B, n = state["joint_pos"].shape
         dev = state["joint_pos"].device
@@ -1055,9 +1094,15 @@ class Handle:
             status = torch.empty((B,), dtype=torch.int32, device=dev)
         np_ = _ptr(nu, torch.float64, (B, 6 + n), "nu") if nu is not False else None
         sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
-        _check(lib().blf_fb_ik_integrate(self._h, ctypes.byref(dm.c),
-                                         ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c), B,
-                                         int(steps), float(dT), np_, sp, _stream(stream)))
+        if hard is None:
+            _check(lib().blf_fb_ik_integrate(self._h, ctypes.byref(dm.c),
+                                             ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c), B,
+                                             int(steps), float(dT), np_, sp, _stream(stream)))
+        else:
+            _check(lib().blf_fb_ik_integrate_hard(self._h, ctypes.byref(dm.c),
+                                                  ctypes.byref(self._fb_state(state, B, n)),
+                                                  ctypes.byref(tasks.c), ctypes.byref(hard), B, int(steps),
+                                                  float(dT), np_, sp, _stream(stream)))
         return state, (nu if nu is not False else None), (status if status is not False else None)
 
     # ---- config 5: the closed loop's maps ----------------------------------

@@ -288,6 +288,14 @@ def standing_ik_tasks(model, states, se3_weight=10.0, com_weight=10.0, joint_wei
                 base_damping=float(base_damping))
 
 
+def standing_ik_hard(model):
+    """The hard rows that go with standing_ik_tasks (native.Handle.ik_hard arguments): every row of
+    both sole tasks, and the CoM's x and y rows; the CoM height, the posture and the base damping
+    stay weighted."""
+    F = len(model["frame_link"])
+    return dict(se3=[[True] * 6 for _ in range(F)], com=[True, True, False])
+
+
 def joint_inertias(model):
     """Composite inertia of every joint's subtree about the joint axis at the nominal posture
     (joints 0, base identity): sum over the subtree's links of z^T R I_c R^T z + m |z x (c - o)|^2."""

@@ -826,9 +826,10 @@ blf_status blf_fbd_euler_integrate(blf_handle* handle, const blf_fb_model* model
 // The checks blf_fb_ik_solve and blf_fb_ik_integrate share.  The shared weight and gain arrays are
 // device memory: they are copied to the host on the call's stream and checked there before the
 // launch (section 12: a staged copy).
+// wout (or null): receives the staged se3_weight 6K | se3_kp 2K | com_weight 3 when batch > 0.
 static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_model* model,
                            const blf_fb_state* state, const blf_ik_tasks* t, int64_t batch,
-                           hipStream_t s)
+                           hipStream_t s, double* wout = nullptr)
 {
     BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
     BLF_REQUIRE(model != nullptr && state != nullptr, "%s: null model / state", fn);
@@ -889,6 +890,43 @@ static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_mode
     }
     if (fb_ik_lds_bytes(n, K) > 160 * 1024)
         return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    if (wout)
+        for (int i = 0; i < jw0; ++i) wout[i] = hbuf[i];
+    return BLF_OK;
+}
+
+// Section 12b's checks after check_ik's: the mask against the task set (and, when batch > 0, against
+// the staged weights), reserved and rel_pivot_min.  Leaves the kernel's row bits in *slots (0: the
+// soft path) and the pivot bound in *tau.
+static blf_status check_ik_hard(const char* fn, blf_handle* handle, const blf_fb_model* model,
+                                const blf_fb_state* state, const blf_ik_tasks* t, const blf_ik_hard* hard,
+                                int64_t batch, hipStream_t s, uint32_t* slots, double* tau)
+{
+    double w[8 * BLF_IK_MAX_SE3_TASKS + 3];
+    const blf_status st = check_ik(fn, handle, model, state, t, batch, s, w);
+    if (st != BLF_OK) return st;
+    *slots = 0;
+    *tau = 0.0;
+    if (hard == nullptr) return BLF_OK;
+    BLF_REQUIRE(hard->reserved == 0, "%s: hard->reserved must be 0", fn);
+    BLF_REQUIRE(std::isfinite(hard->rel_pivot_min) && hard->rel_pivot_min >= 0.0 && hard->rel_pivot_min < 1.0,
+                "%s: rel_pivot_min=%g, must be finite and in [0, 1)", fn, hard->rel_pivot_min);
+    const uint32_t rows = hard->rows;
+    const int K = t->nse3;
+    BLF_REQUIRE((rows >> 27) == 0u, "%s: hard->rows=0x%x has bits above 26", fn, rows);
+    const uint32_t se3 = rows & 0xffffffu, com = rows >> 24;
+    BLF_REQUIRE((se3 >> (6 * K)) == 0u, "%s: hard->rows=0x%x names an SE3 task >= nse3=%d", fn, rows, K);
+    BLF_REQUIRE(com == 0u || t->com_weight != nullptr, "%s: hard->rows=0x%x marks CoM rows without a CoM task",
+                fn, rows);
+    if (batch > 0) {
+        for (int r = 0; r < 6 * K; ++r)
+            BLF_REQUIRE(!((se3 >> r) & 1u) || w[r] > 0.0, "%s: hard row %d of SE3 task %d has weight 0", fn,
+                        r % 6, r / 6);
+        for (int a = 0; a < 3; ++a)
+            BLF_REQUIRE(!((com >> a) & 1u) || w[8 * K + a] > 0.0, "%s: hard CoM row %d has weight 0", fn, a);
+    }
+    *slots = se3 | (com << (6 * K));
+    *tau = hard->rel_pivot_min > 0.0 ? hard->rel_pivot_min : 1.0e-8;
     return BLF_OK;
 }
 
@@ -914,6 +952,34 @@ blf_status blf_fb_ik_integrate(blf_handle* handle, const blf_fb_model* model, co
     if (st != BLF_OK) return st;
     BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel), "blf_fb_ik_integrate: null state buffer");
     return launch_fb_ik(model, state, tasks, batch, steps, dT, nu, status, (hipStream_t)stream);
+}
+
+blf_status blf_fb_ik_solve_hard(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                                const blf_ik_tasks* tasks, const blf_ik_hard* hard, int64_t batch, double* nu,
+                                int32_t* status, void* stream)
+{
+    uint32_t slots = 0;
+    double tau = 0.0;
+    const blf_status st = check_ik_hard("blf_fb_ik_solve_hard", handle, model, state, tasks, hard, batch,
+                                        (hipStream_t)stream, &slots, &tau);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch == 0 || nu != nullptr, "blf_fb_ik_solve_hard: null nu");
+    return launch_fb_ik(model, state, tasks, batch, 0, 0.0, nu, status, (hipStream_t)stream, slots, tau);
+}
+
+blf_status blf_fb_ik_integrate_hard(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                                    const blf_ik_tasks* tasks, const blf_ik_hard* hard, int64_t batch,
+                                    int32_t steps, double dT, double* nu, int32_t* status, void* stream)
+{
+    BLF_REQUIRE(steps >= 1, "blf_fb_ik_integrate_hard: steps=%d, must be >= 1", steps);
+    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_fb_ik_integrate_hard: dT=%g, must be finite and positive", dT);
+    uint32_t slots = 0;
+    double tau = 0.0;
+    const blf_status st = check_ik_hard("blf_fb_ik_integrate_hard", handle, model, state, tasks, hard, batch,
+                                        (hipStream_t)stream, &slots, &tau);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel), "blf_fb_ik_integrate_hard: null state buffer");
+    return launch_fb_ik(model, state, tasks, batch, steps, dT, nu, status, (hipStream_t)stream, slots, tau);
 }
 
 }  // extern "C"

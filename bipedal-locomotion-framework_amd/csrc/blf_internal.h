@@ -143,9 +143,12 @@ blf_status launch_fb_dcm(const blf_fb_model* md, const blf_fb_state* st, const d
 blf_status launch_fb_frame_state(const blf_fb_model* md, const blf_fb_state* st, int32_t K,
                                  const int32_t* frames, int64_t batch, double* pose, double* twist,
                                  hipStream_t s);
-// steps == 0: blf_fb_ik_solve; steps >= 1: blf_fb_ik_integrate
+// steps == 0: blf_fb_ik_solve; steps >= 1: blf_fb_ik_integrate.  slots: section 12b's hard rows as
+// bits of the task-row table (bit 6 K + a: CoM row a), 0: none (the kernels of section 12); tau: the
+// relative pivot bound of S
 blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t, int64_t batch,
-                        int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s);
+                        int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s,
+                        uint32_t slots = 0, double tau = 0.0);
 size_t fb_ik_lds_bytes(int n, int K);
 blf_status launch_posture_reference(const blf_posture_law* law, const double* com, const double* vrp,
                                     int64_t vstride, int64_t batch, double* qref, hipStream_t s);

@@ -10,6 +10,9 @@
 //      task rows read back as LDS broadcasts (dense: structurally zero columns are not skipped);
 //      g_i alongside;
 //   4. Cholesky and the two substitutions: fbd_eval's steps 8-9 (the IK's own copy);
+//      HARD kernels (section 12b), between the substitutions: the hard rows through the forward
+//      substitution, S = Y^T Y lane per row, its Cholesky with the relative pivot rule, lambda, and
+//      z - Y lambda into the backward substitution;
 //   5. nu to LDS (S.rhs()), from where the Euler step or the store takes it.
 // Built without the iterative-ILP scheduler of fb_dynamics.hip: LLVM's register allocator crashes
 // on the 54-row instantiation with it (the reason this kernel has a file of its own).
@@ -25,6 +28,13 @@ struct IkTasks {
     const int32_t* frame;
     const double *w, *kp, *pose, *twist, *cw, *cpos, *cvel, *jw, *jkp, *jpos, *jvel;
     double ckp, damp;
+};
+
+// Section 12b's hard rows as the kernel takes them: bit t marks row t of the task-row table (the
+// CoM bits moved down to 6 K), and the relative pivot bound of S.  Read by the HARD kernels only.
+struct IkHard {
+    unsigned slots;
+    double tau;
 };
 
 constexpr int kIkRows = 6 * BLF_IK_MAX_SE3_TASKS + 3;   // task rows at most
@@ -66,8 +76,10 @@ struct IkSmem {
 
 // One solve for the robot whose state sits in S.st() (zero velocities | bp | bR | jp) and whose
 // set points sit in I.sp().  Leaves nu in S.rhs(); false if a pivot was not finite and positive.
-template <int NVMAX, int HW, bool PRI>
-__device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const IkTasks& tk, const Topo& T)
+// HARD (section 12b): the rows of hd.slots hold exactly; hdep: a pivot of S failed its rule.
+template <int NVMAX, int HW, bool PRI, bool HARD>
+__device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const IkTasks& tk, const Topo& T,
+                                         const IkHard& hd, bool& hdep)
 {
     static_assert(NVMAX <= HW, "a robot's rows must fit its lanes");
     const Half<HW> H;
@@ -257,6 +269,143 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
         const double f = lane > k ? r[k] : 0.0;
         y = y - f * xk;
     }
+    if constexpr (HARD) {
+        // 4b. the hard rows (section 12b).  L's rows are still in r[], z = L^-1 g in y, and the task
+        //     rows intact in I.rows().  Hard row i (in row order) belongs to lane i from step (ii) on.
+        const unsigned hm = hd.slots;   // wave-uniform
+        const int mh = __builtin_popcount(hm);
+        bool hok = mh <= NV;   // more hard rows than unknowns: dependent (and the factor would not fit)
+        if (hok) {
+            double* rows = I.rows();
+            const int cl = lane < NVMAX ? lane : 0;
+            // (i) Y = L^-1 A_h^T: the forward substitution above on each hard row, three right-hand
+            //     sides at a time (independent chains), y_t written back over row t
+            constexpr int G = 3;
+            for (unsigned rest = hm; rest != 0u;) {
+                int t[G];
+                double v[G];
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    t[g] = rest != 0u ? __builtin_ctz(rest) : -1;
+                    rest = rest != 0u ? rest & (rest - 1u) : 0u;
+                    v[g] = t[g] >= 0 && lane < NV ? rows[t[g] * I.rs + cl] : 0.0;
+                }
+#pragma unroll
+                for (int k = 0; k < NVMAX; ++k) {
+                    const double f = lane > k ? r[k] : 0.0;
+#pragma unroll
+                    for (int g = 0; g < G; ++g) {
+                        v[g] = lane == k ? v[g] * idg : v[g];
+                        const double xk = H.bcast_k(v[g], k);
+                        v[g] = v[g] - f * xk;
+                    }
+                }
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    if (t[g] >= 0 && lane < NVMAX) rows[t[g] * I.rs + lane] = v[g];
+            }
+            if (lane < NV) S.rhs()[lane] = y;   // z, for the lanes of (ii)
+            wave_sync();
+            // (ii) lane i < m_h: row i of S = Y^T Y, indexed by table row (entries of soft rows stay
+            //      0 and are never read), and q_i = y_i . z - b_i
+            int own = 0;
+            {
+                int p = 0;
+#pragma unroll
+                for (int t = 0; t < kIkRows; ++t)
+                    if ((hm >> t) & 1u) {
+                        own = lane == p ? t : own;
+                        ++p;
+                    }
+            }
+            double sr[kIkRows], q = 0.0;
+#pragma unroll
+            for (int t = 0; t < kIkRows; ++t) sr[t] = 0.0;
+            {
+                const double* yo = rows + own * I.rs;
+                const double* z = S.rhs();
+                for (int c = 0; c < NV; ++c) {
+                    const double yi = yo[c];
+                    q = fma(yi, z[c], q);
+#pragma unroll
+                    for (int t = 0; t < kIkRows; ++t)
+                        if ((hm >> t) & 1u) sr[t] = fma(yi, rows[t * I.rs + c], sr[t]);
+                }
+                q = q - I.wt()[kIkRows + own];
+            }
+            double d0 = 0.0;   // S_ii before elimination
+#pragma unroll
+            for (int t = 0; t < kIkRows; ++t) d0 = own == t ? sr[t] : d0;
+            // (iii) S = C C^T, lane per row: pivot p (table row t) is lane p's sr[t]; column p of C
+            //       goes to LDS packed (entries p..m_h-1), over the link records, which are dead
+            //       until the next kinematics: m_h (m_h + 1) / 2 <= 27 (n + 1) since m_h <= min(27, NV)
+            double* ct = S.link();
+            double cdi = 0.0;   // 1 / C_ii of the lane's own row
+            {
+                int p = 0;
+#pragma unroll
+                for (int t = 0; t < kIkRows; ++t)
+                    if ((hm >> t) & 1u) {
+                        const double d = H.bcast_k(sr[t], p);
+                        const double dd = H.bcast_k(d0, p);
+                        hok = hok && (d > hd.tau * dd) && (d <= 1.7976931348623157e308);
+                        const double qq = __builtin_amdgcn_rsq(d);
+                        const double il = qq * (1.5 - (0.5 * d) * (qq * qq));
+                        const double l = sr[t] * il;
+                        sr[t] = l;
+                        cdi = lane == p ? il : cdi;
+                        double* col = ct + (p * mh - (p * (p - 1)) / 2);
+                        if (lane >= p && lane < mh) col[lane - p] = l;
+                        wave_sync();
+                        int pu = 1;
+#pragma unroll
+                        for (int u = t + 1; u < kIkRows; ++u)
+                            if ((hm >> u) & 1u) {
+                                sr[u] = fma(-l, col[pu], sr[u]);
+                                ++pu;
+                            }
+                        ++p;
+                    }
+            }
+            // (iv) lambda = C^-T C^-1 q
+            {
+                int p = 0;
+#pragma unroll
+                for (int t = 0; t < kIkRows; ++t)
+                    if ((hm >> t) & 1u) {
+                        q = lane == p ? q * cdi : q;
+                        const double xk = H.bcast_k(q, p);
+                        const double f = lane > p ? sr[t] : 0.0;
+                        q = q - f * xk;
+                        ++p;
+                    }
+            }
+            {
+                const int li = lane < mh ? lane : 0;
+                const double* mycol = ct + (li * mh - (li * (li - 1)) / 2) - li;   // C[p][lane] at [p]
+                for (int p = mh - 1; p >= 0; --p) {
+                    q = lane == p ? q * cdi : q;
+                    const double xk = H.bcast_k(q, p);
+                    const double f = lane < p ? mycol[p] : 0.0;
+                    q = q - f * xk;
+                }
+            }
+            // (v) z - Y lambda
+            {
+                int p = 0;
+#pragma unroll
+                for (int t = 0; t < kIkRows; ++t)
+                    if ((hm >> t) & 1u) {
+                        const double lam = H.bcast_k(q, p);
+                        const double yt = lane < NV ? rows[t * I.rs + cl] : 0.0;
+                        y = y - yt * lam;
+                        ++p;
+                    }
+            }
+            wave_sync();   // the rows are read; L goes over them next
+        }
+        hdep = !hok;
+    }
     double* Lr = I.rows();
     if (lane < NV)
 #pragma unroll
@@ -279,10 +428,10 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
 
 // blf_fb_ik_solve (steps == 0) and blf_fb_ik_integrate (steps >= 1): the set points staged in LDS
 // once, the state in LDS over all the steps.
-template <int NVMAX, int HW, bool PRI>
+template <int NVMAX, int HW, bool PRI, bool HARD>
 __global__ __launch_bounds__(64) void fb_ik_kernel(Model m, blf_fb_state st, IkTasks tk, int32_t steps,
                                                    double dT, double* __restrict__ nu,
-                                                   int32_t* __restrict__ status, int64_t batch)
+                                                   int32_t* __restrict__ status, int64_t batch, IkHard hd)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const Half<HW> H;
@@ -332,8 +481,11 @@ __global__ __launch_bounds__(64) void fb_ik_kernel(Model m, blf_fb_state st, IkT
         bool sfin = true;
         for (int i = lane; i < 12 + n; i += HW) sfin = sfin && so3_finite(loc[6 + n + i]);
         const bool bad = spbad || H.ballot(!sfin) != 0ull;
-        const bool ok = ik_solve<NVMAX, HW, PRI>(m, I, tk, T);
-        const int s1 = bad ? BLF_IK_BAD_INPUT : ok ? BLF_IK_OK : BLF_IK_NOT_POSITIVE;
+        bool hdep = false;
+        const bool ok = ik_solve<NVMAX, HW, PRI, HARD>(m, I, tk, T, hd, hdep);
+        const int s1 = bad ? BLF_IK_BAD_INPUT
+                       : !ok ? BLF_IK_NOT_POSITIVE
+                       : HARD && hdep ? BLF_IK_HARD_DEPENDENT : BLF_IK_OK;
         stat = alive ? s1 : stat;
         if (steps > 0) {
             // one step of blf_fbk_euler_integrate with nu as its input; a failed robot stays where it is
@@ -380,8 +532,10 @@ size_t fb_ik_lds_bytes(int n, int K)
                        : sizeof(double) * IkSmem(nullptr, n, K, BLF_FBD_MAX_DOFS + 6).total;
 }
 
+// slots == 0: the soft kernels (section 12); otherwise the HARD ones (section 12b)
 blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t, int64_t batch,
-                        int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s)
+                        int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s,
+                        uint32_t slots, double tau)
 {
     if (batch == 0) return BLF_OK;
     IkTasks tk;
@@ -402,15 +556,19 @@ blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const bl
     tk.damp = t->base_damping;
     const bool pri = md->joint_type != nullptr;
     const size_t lds = fb_ik_lds_bytes(md->ndof, tk.K);
-    if (md->ndof + 6 <= 32)
-        hipLaunchKernelGGL((pri ? fb_ik_kernel<32, 32, true> : fb_ik_kernel<32, 32, false>),
-                           dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), lds, s, to_model(md), *st, tk, steps,
-                           dT, nu, status, batch);
-    else
-        hipLaunchKernelGGL((pri ? fb_ik_kernel<BLF_FBD_MAX_DOFS + 6, kWave, true>
-                                : fb_ik_kernel<BLF_FBD_MAX_DOFS + 6, kWave, false>),
-                           dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, tk, steps, dT, nu,
-                           status, batch);
+    const IkHard hd{slots, tau};
+    constexpr int NW = BLF_FBD_MAX_DOFS + 6;
+    if (md->ndof + 6 <= 32) {
+        auto kern = slots ? (pri ? fb_ik_kernel<32, 32, true, true> : fb_ik_kernel<32, 32, false, true>)
+                          : (pri ? fb_ik_kernel<32, 32, true, false> : fb_ik_kernel<32, 32, false, false>);
+        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), lds, s, to_model(md), *st, tk,
+                           steps, dT, nu, status, batch, hd);
+    } else {
+        auto kern = slots ? (pri ? fb_ik_kernel<NW, kWave, true, true> : fb_ik_kernel<NW, kWave, false, true>)
+                          : (pri ? fb_ik_kernel<NW, kWave, true, false> : fb_ik_kernel<NW, kWave, false, false>);
+        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, tk, steps, dT, nu,
+                           status, batch, hd);
+    }
     return check_hip(hipGetLastError(), "fb_ik_kernel launch");
 }
 

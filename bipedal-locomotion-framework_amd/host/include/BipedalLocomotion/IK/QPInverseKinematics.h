@@ -3,16 +3,22 @@
  * Upstream's IK::QPInverseKinematics over SE3Task, CoMTask and JointTrackingTask, for one robot:
  * advance() solves for the generalized velocity nu = (base mixed twist, joint velocities) that
  * minimises the weighted task errors at the robot state, on the device (blf_fb_ik_solve,
- * include/blf/blf_c.h section 12).  Integrating that velocity with
+ * include/blf/blf_c.h section 12), subject to the hard (priority 0) tasks holding exactly
+ * (blf_fb_ik_solve_hard, section 12b).  Integrating that velocity with
  * ForwardEuler<FloatingBaseSystemKinematics> and feeding the state back with setRobotState() is
- * upstream's IntegrationBasedIK loop; blf_fb_ik_integrate runs the same loop in one launch.
+ * upstream's IntegrationBasedIK loop; blf_fb_ik_integrate(_hard) runs the same loop in one launch.
  *
- * Differences from upstream a user can notice: only weighted (priority 1) tasks: addTask() with
- * priority 0 returns false; at most BLF_IK_MAX_SE3_TASKS SE3 tasks, one CoM task and one joint
- * tracking task, which is required (it makes the problem positive definite); the robot is a
+ * Differences from upstream a user can notice: priority 0 (hard) is for SE3Task and CoMTask only
+ * and always covers every row of the task (a mask over single rows is the C ABI's); hard tasks that
+ * are linearly dependent, conflicting or more than 6 + n rows make advance() return false instead
+ * of leaving the choice to a QP solver; there are no inequality tasks and no priorities above 1; at
+ * most BLF_IK_MAX_SE3_TASKS SE3 tasks, one CoM task and one joint
+ * tracking task, which is required and weighted (it makes the problem positive definite); the robot is a
  * blf::RobotModel set with setRobotModel() (no iDynTree KinDynComputations) and its state is given
  * with setRobotState(); set points and the state hold blf::Transform / blf::Vector6 (no manif
- * types); the optional key "base_damping" (default 0) is added to the base diagonal.
+ * types); the optional key "base_damping" (default 0) is added to the base diagonal; the optional
+ * key "hard_task_weight" (default 1) is the weight a hard task's rows enter H with, which
+ * conditions the factorization and does not change the solution.
  */
 #ifndef BLF_BIPEDAL_LOCOMOTION_IK_QP_INVERSE_KINEMATICS_H
 #define BLF_BIPEDAL_LOCOMOTION_IK_QP_INVERSE_KINEMATICS_H
@@ -45,8 +51,9 @@ struct IntegrationBasedIKState
 class QPInverseKinematics : public System::Advanceable<IntegrationBasedIKState>
 {
 public:
-    /** Optional key "base_damping" (finite, >= 0; default 0).  False if the handler is expired or
-     * the value is out of range. */
+    /** Optional keys "base_damping" (finite, >= 0; default 0) and "hard_task_weight" (finite, > 0;
+     * default 1; read by the addTask() calls that follow).  False if the handler is expired or a
+     * value is out of range. */
     bool initialize(std::weak_ptr<ParametersHandler::IParametersHandler> handler);
 
     /** The robot (replaces upstream's KinDynComputations) and, optionally, the names of its frames
@@ -59,11 +66,12 @@ public:
                        const blf::VectorXd& jointPositions);
 
     /**
-     * Add a task.  priority must be 1 (weighted); weight holds one entry per task row (SE3: 6,
-     * linear xyz then angular xyz; CoM: 3; joint tracking: one per joint, > 0), each finite and
-     * >= 0.  False with a "[QPInverseKinematics::addTask] ..." line for priority 0 (or any other
-     * value), a null task, a duplicate name, a wrong weight, a fifth SE3 task, a second CoM or
-     * joint tracking task, or after finalize().
+     * Add a task.  Priority 1 (weighted): weight holds one entry per task row (SE3: 6, linear xyz
+     * then angular xyz; CoM: 3; joint tracking: one per joint, > 0), each finite and >= 0.
+     * Priority 0 (hard: every row of the task holds exactly): an SE3Task or a CoMTask, with an
+     * empty weight.  False with a "[QPInverseKinematics::addTask] ..." line for any other
+     * priority, priority 0 with a weight or for a JointTrackingTask, a null task, a duplicate name,
+     * a wrong weight, a fifth SE3 task, a second CoM or joint tracking task, or after finalize().
      */
     bool addTask(std::shared_ptr<IKLinearTask> task, const std::string& taskName, unsigned int priority,
                  const blf::VectorXd& weight = blf::VectorXd());
@@ -75,7 +83,8 @@ public:
 
     /** Solve at the robot state with the tasks' current set points.  False before finalize() or
      * setRobotState(), without a joint tracking task, when a task has no set point or a wrong size,
-     * or when the device reports a failed solve (the state is then invalid). */
+     * or when the device reports a failed solve, dependent hard tasks (BLF_IK_HARD_DEPENDENT)
+     * among them (the state is then invalid). */
     bool advance() final;
     const IntegrationBasedIKState& get() const final { return m_state; }
     bool isValid() const final { return m_isValid; }
@@ -85,6 +94,11 @@ public:
     const blf_fb_model& deviceModel() const { return m_cModel; }
     const blf_fb_state& deviceState() const { return m_cState; }
     const blf_ik_tasks& deviceTasks() const { return m_cTasks; }
+    const blf_ik_hard& deviceHard() const { return m_cHard; }
+
+    /** Section 12b's mask of the hard tasks added so far: bits 6k..6k+5 for the k-th SE3 task (in
+     * the order they were added) when it is hard, bits 24..26 for a hard CoM task. */
+    uint32_t hardRows() const;
 
 private:
     struct Entry
@@ -92,12 +106,13 @@ private:
         std::string name;
         std::shared_ptr<IKLinearTask> task;
         std::vector<double> weight;
+        bool hard;
     };
     std::vector<Entry> m_tasks;
     std::vector<int32_t> m_frames;
     int m_comTask{-1}, m_jointTask{-1};
     bool m_isFinalized{false}, m_hasModel{false}, m_hasState{false}, m_isValid{false};
-    double m_baseDamping{0.0};
+    double m_baseDamping{0.0}, m_hardWeight{1.0};
     blf::RobotModel m_model;
     std::vector<std::string> m_frameNames;
     blf::Vector3 m_basePosition{};
@@ -111,6 +126,7 @@ private:
     blf_fb_model m_cModel{};
     blf_fb_state m_cState{};
     blf_ik_tasks m_cTasks{};
+    blf_ik_hard m_cHard{};
 };
 
 } // namespace IK

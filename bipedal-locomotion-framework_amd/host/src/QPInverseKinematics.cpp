@@ -1,7 +1,8 @@
 /**
  * @file QPInverseKinematics.cpp
  * The task bookkeeping of IK::QPInverseKinematics on the host; every advance() is one
- * blf_fb_ik_solve for one robot (include/blf/blf_c.h section 12).
+ * blf_fb_ik_solve, or with hard tasks blf_fb_ik_solve_hard, for one robot (include/blf/blf_c.h
+ * sections 12 and 12b).
  */
 #include <algorithm>
 #include <cmath>
@@ -28,7 +29,15 @@ bool QPInverseKinematics::initialize(std::weak_ptr<IParametersHandler> handlerWe
                   << std::endl;
         return false;
     }
+    double hardWeight = 1.0;
+    if (handler->getParameter("hard_task_weight", hardWeight) && (!std::isfinite(hardWeight) || hardWeight <= 0.0))
+    {
+        std::cerr << "[QPInverseKinematics::initialize] The hard_task_weight must be a positive number."
+                  << std::endl;
+        return false;
+    }
     m_baseDamping = damping;
+    m_hardWeight = hardWeight;
     return true;
 }
 
@@ -130,11 +139,23 @@ bool QPInverseKinematics::addTask(std::shared_ptr<IKLinearTask> task, const std:
         std::cerr << where << "The task " << taskName << " is not valid (null pointer)." << std::endl;
         return false;
     }
-    if (priority != 1)
+    if (priority > 1)
     {
         std::cerr << where << "The task " << taskName << " has priority " << priority
-                  << ": only weighted tasks (priority 1) are supported; hard constraints (priority 0) "
-                     "are not."
+                  << ": only hard (priority 0) and weighted (priority 1) tasks are supported." << std::endl;
+        return false;
+    }
+    const bool hard = priority == 0;
+    if (hard && weight.size() != 0)
+    {
+        std::cerr << where << "The task " << taskName << " has priority 0: a hard task takes no weight."
+                  << std::endl;
+        return false;
+    }
+    if (hard && task->kind() == IKLinearTask::Kind::JointTracking)
+    {
+        std::cerr << where << "The task " << taskName << " is the joint tracking task, the regulariser: it "
+                     "cannot be hard (priority 0)."
                   << std::endl;
         return false;
     }
@@ -164,6 +185,12 @@ bool QPInverseKinematics::addTask(std::shared_ptr<IKLinearTask> task, const std:
     }
     const bool joint = kind == IKLinearTask::Kind::JointTracking;
     const std::size_t rows = kind == IKLinearTask::Kind::SE3 ? 6 : kind == IKLinearTask::Kind::CoM ? 3 : weight.size();
+    if (hard)
+    {
+        if (kind == IKLinearTask::Kind::CoM) m_comTask = static_cast<int>(m_tasks.size());
+        m_tasks.push_back(Entry{taskName, std::move(task), std::vector<double>(rows, m_hardWeight), true});
+        return true;
+    }
     if (weight.size() != rows || rows == 0)
     {
         std::cerr << where << "The weight of the task " << taskName << " has " << weight.size()
@@ -179,8 +206,26 @@ bool QPInverseKinematics::addTask(std::shared_ptr<IKLinearTask> task, const std:
         }
     if (kind == IKLinearTask::Kind::CoM) m_comTask = static_cast<int>(m_tasks.size());
     if (joint) m_jointTask = static_cast<int>(m_tasks.size());
-    m_tasks.push_back(Entry{taskName, std::move(task), std::vector<double>(weight.data(), weight.data() + rows)});
+    m_tasks.push_back(Entry{taskName, std::move(task), std::vector<double>(weight.data(), weight.data() + rows),
+                            false});
     return true;
+}
+
+uint32_t QPInverseKinematics::hardRows() const
+{
+    uint32_t rows = 0;
+    int k = 0;
+    for (const Entry& e : m_tasks)
+    {
+        if (e.task->kind() == IKLinearTask::Kind::SE3)
+        {
+            if (e.hard) rows |= 0x3fu << (6 * k);
+            ++k;
+        }
+        else if (e.task->kind() == IKLinearTask::Kind::CoM && e.hard)
+            rows |= 0x7u << 24;
+    }
+    return rows;
 }
 
 std::vector<std::string> QPInverseKinematics::getTaskNames() const
@@ -348,16 +393,22 @@ bool QPInverseKinematics::advance()
     m_cTasks.joint_vel = d + oJv;
     m_cTasks.base_damping = m_baseDamping;
     int32_t* status = m_dInt.data() + K;
-    if (!blf::report(blf_fb_ik_solve(h, &m_cModel, &m_cState, &m_cTasks, 1, d, status, nullptr),
-                     "QPInverseKinematics::advance"))
-        return false;
+    m_cHard = blf_ik_hard{};
+    m_cHard.rows = hardRows();
+    const blf_status called = m_cHard.rows != 0
+                                  ? blf_fb_ik_solve_hard(h, &m_cModel, &m_cState, &m_cTasks, &m_cHard, 1, d, status,
+                                                         nullptr)
+                                  : blf_fb_ik_solve(h, &m_cModel, &m_cState, &m_cTasks, 1, d, status, nullptr);
+    if (!blf::report(called, "QPInverseKinematics::advance")) return false;
     std::vector<double> nu(NV);
     if (!m_dData.download(nu.data(), NV) || !m_dInt.download(ints.data(), K + 1)) return false;
     if (ints[K] != BLF_IK_OK)
     {
         std::cerr << where
                   << (ints[K] == BLF_IK_BAD_INPUT ? "The robot state or a set point is not finite."
-                                                  : "The problem is not positive definite.")
+                      : ints[K] == BLF_IK_HARD_DEPENDENT
+                          ? "The hard tasks are linearly dependent, conflicting or more than the unknowns."
+                          : "The problem is not positive definite.")
                   << std::endl;
         return false;
     }

@@ -96,7 +96,8 @@ blf_status blf_destroy(blf_handle* handle);
 const char* blf_last_error(void);
 /* Version string of the library: "blf-mi355x <version> (abi <n>, ...) src <hash>".  ABI 3 (0.3.0)
  * is additive: it adds blf_rls_advance and blf_contact_rls_advance and changes no existing entry
- * point or struct.  blf_swing_foot_eval and blf_so3_eval were added within ABI 3 (no existing
+ * point or struct.  blf_swing_foot_eval and blf_so3_eval, and later blf_fb_ik_solve_hard and
+ * blf_fb_ik_integrate_hard (section 12b), were added within ABI 3 (no existing
  * entry point or struct changed, so the number stays): a caller detects them by symbol
  * (dlsym).  ABI 2 (0.2.0) added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
  * a caller built against an older header must zero-initialise these structs (`= {0}`), since the
@@ -774,6 +775,52 @@ blf_status blf_fb_ik_integrate(blf_handle* handle, const blf_fb_model* model,
                                double* nu /* [B][6+n], the last step's, or NULL */,
                                int32_t* status /* [B] or NULL: the first non-zero of the steps */,
                                void* stream);
+
+/* ---- 12b. Hard (priority-0) tasks: task rows held as exact equality constraints ----
+ * Section 12 defines the task rows a_r, their weights w_r and their targets t_r.  A 27-bit mask
+ * `rows` marks some of them hard: bit 6k + a marks row a of SE3 task k (linear xyz, angular xyz),
+ * bits 24 to 26 mark the CoM rows.  With A_h and b_h the hard rows and their targets, in row order,
+ * m_h <= 27, the solve is
+ *   minimise   1/2 sum_soft w_r (a_r nu - t_r)^2 + joint-tracking and base-damping terms of section 12
+ *   subject to A_h nu = b_h,
+ * computed as follows:
+ *   1. H and g are assembled exactly as section 12 assembles them: hard rows are included with their
+ *      weights, in the same order and with the same fmas.  A hard row's weight only conditions H; in
+ *      exact arithmetic the result does not depend on it.
+ *   2. H = L L^T with section 12's factorization;  z = L^-1 g;  Y = L^-1 A_h^T.
+ *   3. S = Y^T Y (m_h x m_h) is factorized by Cholesky with a relative pivot rule: pivot i must
+ *      satisfy d_i > tau * S_ii, S_ii the entry before elimination (and be finite); tau = 1e-8 by
+ *      default.
+ *   4. lambda = S^-1 (Y^T z - b_h)  and  nu = L^-T (z - Y lambda).
+ * Every hard row also enters H, so H is positive definite whenever the constrained problem is well
+ * posed, even with base_damping = 0 and the base held only by hard feet.
+ * Per-robot status: section 12's, and BLF_IK_HARD_DEPENDENT when a pivot of S fails the rule (the
+ * hard rows are linearly dependent, conflicting, or more than 6 + n): nu = NaN, other robots are
+ * untouched.  When several apply: BLF_IK_BAD_INPUT, then BLF_IK_NOT_POSITIVE, then
+ * BLF_IK_HARD_DEPENDENT.  blf_fb_ik_integrate_hard treats it like any failed step (section 12), and
+ * is bit for bit `steps` x { blf_fb_ik_solve_hard; blf_fbk_euler_integrate(0, dT, dT) }.
+ * hard == NULL or rows == 0: exactly blf_fb_ik_solve / blf_fb_ik_integrate, bit for bit.
+ * Call-level errors: section 12's, and BLF_ERR_INVALID_ARGUMENT for a bit that names an SE3 task
+ * >= nse3, a CoM bit without com_weight, a hard row whose weight is 0 (checked with the staged
+ * weights, so only when batch > 0), bits above 26, reserved != 0, or a rel_pivot_min that is not
+ * finite or outside [0, 1). */
+#define BLF_IK_HARD_DEPENDENT 3   /* a pivot of S failed the rule: dependent / conflicting / too many hard rows */
+typedef struct blf_ik_hard {
+    uint32_t rows;          /* bit 6k+a: row a of SE3 task k; bits 24..26: CoM x, y, z */
+    int32_t  reserved;      /* must be 0 */
+    double   rel_pivot_min; /* tau; 0 selects the default 1e-8; finite, in [0, 1) */
+} blf_ik_hard;
+
+blf_status blf_fb_ik_solve_hard(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                                const blf_ik_tasks* tasks, const blf_ik_hard* hard /* or NULL */,
+                                int64_t batch, double* nu /* [B][6+n] */,
+                                int32_t* status /* [B] or NULL */, void* stream);
+
+blf_status blf_fb_ik_integrate_hard(blf_handle* handle, const blf_fb_model* model,
+                                    const blf_fb_state* state /* in place */, const blf_ik_tasks* tasks,
+                                    const blf_ik_hard* hard /* or NULL */, int64_t batch, int32_t steps,
+                                    double dT, double* nu /* [B][6+n], the last step's, or NULL */,
+                                    int32_t* status /* [B] or NULL */, void* stream);
 
 /* Algorithmic flop count of one IPM iteration of one problem (what the fp64 roofline field
  * of bench.py is computed from); `active_facets` = sum_k nfacets[k]. */

@@ -10,7 +10,10 @@ warm-up, median of `rounds` rounds, the variants alternating within a round.  On
   * as yardsticks at the same B, the two existing kernels the IK is assembled from:
     blf_fb_frame_state (the forward kinematics alone, one robot per wavefront) and blf_fbd_dynamics
     with mass_reg = zeros and no contacts (kinematics, mass matrix, the same Cholesky and
-    substitutions, two robots per wavefront).
+    substitutions, two robots per wavefront);
+  * with --hard, in the same rounds: blf_fb_ik_solve_hard and blf_fb_ik_integrate_hard (steps = 20)
+    with robot.standing_ik_hard (both soles and the CoM's x, y: 14 hard rows), and their ratio to the
+    soft figures of the same run.
 
 Counted flops per robot-step, NV = n + 6, M = the task rows of non-zero weight: H and g from the task
 rows M (NV (NV + 1) + 2 NV), the Cholesky factorization NV^3 / 3, the two substitutions 2 NV^2.  The
@@ -18,7 +21,7 @@ kinematics and the task rows themselves are not counted.  Both calls stage the s
 to the host and wait for that copy before they launch (blf_c.h section 12), so every call here
 includes one stream synchronisation: the unfused sequence pays 20 of them, the fused call one.
 
-  timeout -k 10 600 python tools/ik_bench.py [--robots 16384] [--steps 20] [--rounds 5]
+  timeout -k 10 600 python tools/ik_bench.py [--robots 16384] [--steps 20] [--rounds 5] [--hard]
 (BLF_LIB=.../lib/libblf_<name>.so times a variant build, tools/build_variant.sh)
 """
 import argparse
@@ -72,6 +75,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--label", default="")
+    ap.add_argument("--hard", action="store_true", help="also time the hard-task calls (section 12b)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a HIP device"
     h = native.Handle(0)
@@ -117,11 +121,20 @@ def main():
     ftwist = torch.empty((B, frames.shape[0], 6), dtype=torch.float64, device="cuda")
     tau = torch.zeros((B, n), dtype=torch.float64, device="cuda")
     reg = torch.zeros((NV, NV), dtype=torch.float64, device="cuda")
-    res = compare({"solve": lambda: h.fb_ik_solve(dm, start, tk, nu=nu, status=status), "restore": restore,
-                   "fused": fused, "unfused": unfused,
-                   "frame_state": lambda: h.fb_frame_state(dm, start, frames, pose=fpose, twist=ftwist),
-                   "fbd_dynamics_reg": lambda: h.fbd_dynamics(dm, start, tau, mass_reg=reg)},
-                  reps=args.reps, rounds=args.rounds)
+    variants = {"solve": lambda: h.fb_ik_solve(dm, start, tk, nu=nu, status=status), "restore": restore,
+                "fused": fused, "unfused": unfused,
+                "frame_state": lambda: h.fb_frame_state(dm, start, frames, pose=fpose, twist=ftwist),
+                "fbd_dynamics_reg": lambda: h.fbd_dynamics(dm, start, tau, mass_reg=reg)}
+    if args.hard:
+        hard = h.ik_hard(**robot.standing_ik_hard(model))
+
+        def fused_hard():
+            restore()
+            h.fb_ik_integrate(dm, st, tk, steps, DT, nu=nu, status=status, hard=hard)
+
+        variants["solve_hard"] = lambda: h.fb_ik_solve(dm, start, tk, nu=nu, status=status, hard=hard)
+        variants["fused_hard"] = fused_hard
+    res = compare(variants, reps=args.reps, rounds=args.rounds)
     fused()
     f_state = {k: v.clone() for k, v in st.items()}
     ok_f = bool((status == 0).all())
@@ -141,6 +154,15 @@ def main():
                       "fp64_fraction_fused": B * steps * fl / (f_ms * 1e-3) / FP64_PEAK,
                       "fused_equals_unfused_bitwise": same, "all_status_ok": ok_f,
                       "label": args.label}), flush=True)
+    if args.hard:
+        fused_hard()
+        ok_h = bool((status == 0).all())
+        h_ms = res["fused_hard"][0] - res["restore"][0]
+        print(json.dumps({"bench": "fb_ik_hard", "robots": B, "steps": steps,
+                          "hard_rows": bin(hard.rows).count("1"), "solve_hard_ms": res["solve_hard"],
+                          "fused_hard_ms": res["fused_hard"], "solve_hard_over_soft": res["solve_hard"][0] / res["solve"][0],
+                          "fused_hard_over_soft_net": h_ms / f_ms, "fused_hard_ms_per_step_net": h_ms / steps,
+                          "all_status_ok": ok_h, "label": args.label}), flush=True)
     h.close()
 
 
