@@ -31,7 +31,8 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_fb_dcm", "blf_dcm_posture_reference", "blf_fbd_euler_integrate_impedance",
             "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance",
             "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate",
-            "blf_fb_ik_solve_hard", "blf_fb_ik_integrate_hard"]
+            "blf_fb_ik_solve_hard", "blf_fb_ik_integrate_hard", "blf_fb_ik_solve_limits",
+            "blf_fb_ik_integrate_limits"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -94,8 +95,15 @@ class IkHard(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_uint32), ("reserved", _i32), ("rel_pivot_min", _f64)]
 
 
+class IkLimits(ctypes.Structure):
+    """blf_ik_limits (include/blf/blf_c.h section 12c); every pointer is device memory."""
+    _fields_ = [("pos_lower", _vp), ("pos_upper", _vp), ("klim", _vp), ("vel_max", _vp),
+                ("sampling_time", _f64), ("max_iter", _i32), ("reserved", _i32)]
+
+
 IK_OK, IK_NOT_POSITIVE, IK_BAD_INPUT = 0, 1, 2   # per-robot status of fb_ik_solve / fb_ik_integrate
 IK_HARD_DEPENDENT = 3   # with hard rows: a pivot of S failed the rule (section 12b)
+IK_LIMITS_UNRESOLVED = 4   # with limits: the active-set iteration found no feasible optimal set (section 12c)
 
 SWING_OUTPUTS = ("pose", "twist", "accel", "contact_idx", "in_contact")
 SO3_OUTPUTS = ("rot", "omega", "alpha")
@@ -240,6 +248,13 @@ def lib():
         L.blf_fb_ik_integrate_hard.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
                                                ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard), _i64, _i32, _f64,
                                                _vp, _vp, _vp]
+        L.blf_fb_ik_solve_limits.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
+                                             ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard),
+                                             ctypes.POINTER(IkLimits), _i64, _vp, _vp, _vp, _vp, _vp]
+        L.blf_fb_ik_integrate_limits.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
+                                                 ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard),
+                                                 ctypes.POINTER(IkLimits), _i64, _i32, _f64, _vp, _vp, _vp, _vp,
+                                                 _vp]
         L.blf_dcm_mpc_flops_per_iter.restype = _f64
         L.blf_set_qp_launch_mode.argtypes = [_i32, _i32]
         for name in EXPORTED:
@@ -1056,12 +1071,50 @@ class Handle:
         h.rows, h.reserved, h.rel_pivot_min = rows, 0, float(rel_pivot_min)
         return h
 
-    def fb_ik_solve(self, dm, state, tasks, nu=None, status=None, stream=None, hard=None):
+    def ik_limits(self, pos_lower, pos_upper, klim, vel_max=None, sampling_time=0.01, max_iter=0):
+        """Build a blf_ik_limits (section 12c) for a model of n joints, e.g.
+        **robot.humanoid24_joint_limits(model): pos_lower / pos_upper [n] (-inf / +inf: no limit), klim
+        [n] in (0, 1], vel_max [n] or None, shared by the batch.  Host arrays are uploaded.  Returns an
+        object with the struct (.c) and the tensors (.t) it keeps alive."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+
+        class _T:
+            pass
+        lm = _T()
+        n = int(len(pos_lower))
+        c = IkLimits()
+        lm.t = {}
+        for k, a in (("pos_lower", pos_lower), ("pos_upper", pos_upper), ("klim", klim), ("vel_max", vel_max)):
+            if a is None:
+                continue
+            lm.t[k] = a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=torch.float64).contiguous().to(dev)
+            setattr(c, k, _ptr(lm.t[k], torch.float64, (n,), k))
+        c.sampling_time, c.max_iter, c.reserved = float(sampling_time), int(max_iter), 0
+        lm.c, lm.n = c, n
+        return lm
+
+    def _ik_limits_out(self, B, dev, iters, active):
+        """The iters [B] int32 and active [B,2] int64 outputs of the limits calls (False: not requested)."""
+        torch = _torch()
+        if iters is None:
+            iters = torch.zeros((B,), dtype=torch.int32, device=dev)
+        if active is None:
+            active = torch.zeros((B, 2), dtype=torch.int64, device=dev)
+        ip = _ptr(iters, torch.int32, (B,), "iters") if iters is not False else None
+        ap = _ptr(active, torch.int64, (B, 2), "active") if active is not False else None
+        return iters, active, ip, ap
+
+    def fb_ik_solve(self, dm, state, tasks, nu=None, status=None, stream=None, hard=None, limits=None,
+                    iters=None, active=None):
         """blf_fb_ik_solve: nu [B,6+n] = (base mixed twist, joint velocities) minimising the weighted
         task errors at the state's base_pos / base_rot / joint_pos, and the per-robot status [B]
         int32 (IK_OK / IK_NOT_POSITIVE / IK_BAD_INPUT; status=False: not requested).
         hard (an ik_hard()): blf_fb_ik_solve_hard, the marked rows held exactly (status may then be
-        IK_HARD_DEPENDENT); None: today's call."""
+        IK_HARD_DEPENDENT); None: today's call.
+        limits (an ik_limits()): blf_fb_ik_solve_limits, the joint velocities kept in section 12c's box
+        (status may then be IK_LIMITS_UNRESOLVED); the call then returns (nu, status, iters [B] int32,
+        active [B,2] int64: the joints that end on their lower | upper bound, a bit each)."""
         torch = _torch()
         B, n = state["joint_pos"].shape
         dev = state["joint_pos"].device
@@ -1069,6 +1122,16 @@ class Handle:
         if status is None:
             status = torch.empty((B,), dtype=torch.int32, device=dev)
         sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
+        if limits is not None:
+            iters, active, ip, ap = self._ik_limits_out(B, dev, iters, active)
+            _check(lib().blf_fb_ik_solve_limits(self._h, ctypes.byref(dm.c),
+                                                ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c),
+                                                ctypes.byref(hard) if hard is not None else None,
+                                                ctypes.byref(limits.c), B,
+                                                _ptr(nu, torch.float64, (B, 6 + n), "nu"), sp, ip, ap,
+                                                _stream(stream)))
+            return (nu, (status if status is not False else None), (iters if iters is not False else None),
+                    (active if active is not False else None))
         if hard is None:
             _check(lib().blf_fb_ik_solve(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
                                          ctypes.byref(tasks.c), B, _ptr(nu, torch.float64, (B, 6 + n), "nu"), sp,
@@ -1080,11 +1143,13 @@ class Handle:
                                               sp, _stream(stream)))
         return nu, (status if status is not False else None)
 
-    def fb_ik_integrate(self, dm, state, tasks, steps, dT, nu=None, status=None, stream=None, hard=None):
+    def fb_ik_integrate(self, dm, state, tasks, steps, dT, nu=None, status=None, stream=None, hard=None,
+                        limits=None, iters=None, active=None):
         """blf_fb_ik_integrate: `steps` x (solve, one Euler step of dT) in one launch, in place on
         `state` (base_vel / joint_vel receive the last step's nu).  nu / status as fb_ik_solve;
         False: not requested.  hard as fb_ik_solve (blf_fb_ik_integrate_hard).  Returns (state, nu,
-        status)."""
+        status), and with limits (blf_fb_ik_integrate_limits) also iters (summed over the steps) and
+        active (the last step's)."""
         torch = _torch()
         B, n = state["joint_pos"].shape
         dev = state["joint_pos"].device
@@ -1094,6 +1159,16 @@ class Handle:
             status = torch.empty((B,), dtype=torch.int32, device=dev)
         np_ = _ptr(nu, torch.float64, (B, 6 + n), "nu") if nu is not False else None
         sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
+        if limits is not None:
+            iters, active, ip, ap = self._ik_limits_out(B, dev, iters, active)
+            _check(lib().blf_fb_ik_integrate_limits(self._h, ctypes.byref(dm.c),
+                                                    ctypes.byref(self._fb_state(state, B, n)),
+                                                    ctypes.byref(tasks.c),
+                                                    ctypes.byref(hard) if hard is not None else None,
+                                                    ctypes.byref(limits.c), B, int(steps), float(dT), np_, sp, ip,
+                                                    ap, _stream(stream)))
+            return (state, (nu if nu is not False else None), (status if status is not False else None),
+                    (iters if iters is not False else None), (active if active is not False else None))
         if hard is None:
             _check(lib().blf_fb_ik_integrate(self._h, ctypes.byref(dm.c),
                                              ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c), B,

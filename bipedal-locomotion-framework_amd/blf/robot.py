@@ -296,6 +296,25 @@ def standing_ik_hard(model):
     return dict(se3=[[True] * 6 for _ in range(F)], com=[True, True, False])
 
 
+# joint name's last word(s) -> (lower, upper) rad, velocity limit rad/s.  Positive knee angles fold the
+# leg (the shank swings back), so the knee's range starts at straight.
+_JOINT_RANGE = {"hip_yaw": (-0.8, 0.8, 6.0), "hip_roll": (-0.5, 0.5, 6.0), "hip_pitch": (-1.9, 0.8, 6.0),
+                "knee": (0.0, 2.3, 6.0), "ankle_pitch": (-0.8, 0.8, 6.0), "ankle_roll": (-0.4, 0.4, 6.0),
+                "torso_pitch": (-0.4, 0.9, 4.0), "torso_roll": (-0.5, 0.5, 4.0), "torso_yaw": (-0.9, 0.9, 4.0),
+                "shoulder_pitch": (-2.8, 1.2, 4.0), "shoulder_roll": (-1.6, 1.6, 4.0),
+                "shoulder_yaw": (-1.5, 1.5, 4.0), "elbow": (-2.3, 0.3, 4.0), "neck_pitch": (-0.7, 0.7, 4.0)}
+
+
+def humanoid24_joint_limits(model, klim=0.5, sampling_time=0.01):
+    """Joint ranges and velocity limits of humanoid24 (native.Handle.ik_limits arguments, include/blf/blf_c.h
+    section 12c): pos_lower / pos_upper [n] rad, vel_max [n] rad/s, klim [n], sampling_time."""
+    names = model["names"][1:]   # joint j moves link j + 1
+    rng = [_JOINT_RANGE[nm[2:] if nm[:2] in ("l_", "r_") else nm] for nm in names]
+    lo, up, vm = (np.array(c, dtype=np.float64) for c in zip(*rng))
+    return dict(pos_lower=lo, pos_upper=up, klim=np.full(len(names), float(klim)), vel_max=vm,
+                sampling_time=float(sampling_time))
+
+
 def joint_inertias(model):
     """Composite inertia of every joint's subtree about the joint axis at the nominal posture
     (joints 0, base identity): sum over the subtree's links of z^T R I_c R^T z + m |z x (c - o)|^2."""

@@ -205,3 +205,30 @@ def reorder_joints(model, perm):
     out["frame_link"] = np.asarray([new_link[l] for l in model["frame_link"]], dtype=np.int32)
     out["names"] = [model["names"][0]] + [model["names"][o + 1] for o in perm]
     return out
+
+
+def load_urdf_limits(source, model):
+    """The <limit lower upper velocity> of the joints of `model` (a load_urdf result of the same
+    document, whatever base, considered_joints and merge it was loaded with), in the model's joint
+    order: dict(pos_lower, pos_upper [n] rad or m, vel_max [n]), the position arguments of
+    native.Handle.ik_limits.  A continuous joint, a joint without the tag or without the attribute has
+    -inf / +inf; a missing or non-positive velocity is +inf (no limit).  Kept out of the model dict, whose
+    keys the dynamics' loaders compare."""
+    text = source if isinstance(source, str) and source.lstrip().startswith("<") else open(source).read()
+    joints = {j.get("name"): j for j in ET.fromstring(text).findall("joint")}
+    n = model["n"]
+    lower, upper, vel = np.full(n, -np.inf), np.full(n, np.inf), np.full(n, np.inf)
+    for k, name in enumerate(model["names"][1:]):
+        j = joints[name]
+        lim = j.find("limit")
+        if lim is None:
+            continue
+        if j.get("type") != "continuous":
+            lower[k] = float(lim.get("lower", -np.inf))
+            upper[k] = float(lim.get("upper", np.inf))
+            if lower[k] > upper[k]:
+                raise ValueError(f"load_urdf_limits: joint {name} has a lower limit above its upper limit")
+        v = float(lim.get("velocity", 0.0))
+        if v > 0.0:
+            vel[k] = v
+    return dict(pos_lower=lower, pos_upper=upper, vel_max=vel)

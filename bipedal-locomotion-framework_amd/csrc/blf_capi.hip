@@ -930,7 +930,87 @@ static blf_status check_ik_hard(const char* fn, blf_handle* handle, const blf_fb
     return BLF_OK;
 }
 
+// Section 12c's checks (after check_ik_hard's, batch > 0): the struct's scalars, then the limit arrays
+// through a staged copy like check_ik's.  Leaves the default in *max_iter when the caller gave 0.
+static blf_status check_ik_limits(const char* fn, const blf_ik_limits* lim, int n, hipStream_t s, int32_t* max_iter)
+{
+    BLF_REQUIRE(lim->reserved == 0, "%s: limits->reserved must be 0", fn);
+    BLF_REQUIRE(std::isfinite(lim->sampling_time) && lim->sampling_time > 0.0,
+                "%s: sampling_time=%g, must be finite and positive", fn, lim->sampling_time);
+    BLF_REQUIRE(lim->max_iter >= 0, "%s: max_iter=%d, must be >= 0", fn, lim->max_iter);
+    BLF_REQUIRE(lim->pos_lower && lim->pos_upper && lim->klim, "%s: null limit array", fn);
+    double hbuf[4 * BLF_FBD_MAX_DOFS];
+    const double* src[4] = {lim->pos_lower, lim->pos_upper, lim->klim, lim->vel_max};
+    for (int a = 0; a < 4; ++a) {
+        if (src[a] == nullptr) continue;
+        const blf_status st = check_hip(
+            hipMemcpyAsync(hbuf + a * n, src[a], sizeof(double) * n, hipMemcpyDeviceToHost, s),
+            "blf_fb_ik: staging the joint limits");
+        if (st != BLF_OK) return st;
+    }
+    const blf_status st = check_hip(hipStreamSynchronize(s), "blf_fb_ik: staging the joint limits");
+    if (st != BLF_OK) return st;
+    for (int j = 0; j < n; ++j) {
+        const double lo = hbuf[j], up = hbuf[n + j], kl = hbuf[2 * n + j];
+        BLF_REQUIRE(lo <= up && lo < HUGE_VAL && up > -HUGE_VAL,
+                    "%s: pos_lower[%d]=%g, pos_upper[%d]=%g, must be ordered (and not NaN)", fn, j, lo, j, up);
+        BLF_REQUIRE(kl > 0.0 && kl <= 1.0, "%s: klim[%d]=%g, must be in (0, 1]", fn, j, kl);
+        BLF_REQUIRE(lim->vel_max == nullptr || hbuf[3 * n + j] > 0.0, "%s: vel_max[%d]=%g, must be > 0", fn, j,
+                    lim->vel_max ? hbuf[3 * n + j] : 0.0);
+    }
+    *max_iter = lim->max_iter > 0 ? lim->max_iter : BLF_IK_LIMITS_DEFAULT_MAX_ITER;
+    return BLF_OK;
+}
+
+// blf_fb_ik_solve_limits (steps == 0) and blf_fb_ik_integrate_limits after their own argument checks
+static blf_status ik_limits_call(const char* fn, blf_handle* handle, const blf_fb_model* model,
+                                 const blf_fb_state* state, const blf_ik_tasks* tasks, const blf_ik_hard* hard,
+                                 const blf_ik_limits* limits, int64_t batch, int32_t steps, double dT, double* nu,
+                                 int32_t* status, int32_t* iters, uint64_t* active, hipStream_t s)
+{
+    uint32_t slots = 0;
+    double tau = 0.0;
+    const blf_status st = check_ik_hard(fn, handle, model, state, tasks, hard, batch, s, &slots, &tau);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch == 0 || steps > 0 || nu != nullptr, "%s: null nu", fn);
+    BLF_REQUIRE(batch == 0 || steps == 0 || (state->base_vel && state->joint_vel), "%s: null state buffer", fn);
+    if (limits == nullptr) return launch_fb_ik(model, state, tasks, batch, steps, dT, nu, status, s, slots, tau);
+    blf_ik_limits lim = *limits;
+    if (batch > 0) {
+        const blf_status sl = check_ik_limits(fn, limits, model->ndof, s, &lim.max_iter);
+        if (sl != BLF_OK) return sl;
+        if (fb_ik_lds_bytes(model->ndof, tasks->nse3, true) > 160 * 1024)
+            return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    } else {
+        BLF_REQUIRE(limits->reserved == 0, "%s: limits->reserved must be 0", fn);
+        BLF_REQUIRE(std::isfinite(limits->sampling_time) && limits->sampling_time > 0.0,
+                    "%s: sampling_time=%g, must be finite and positive", fn, limits->sampling_time);
+        BLF_REQUIRE(limits->max_iter >= 0, "%s: max_iter=%d, must be >= 0", fn, limits->max_iter);
+    }
+    return launch_fb_ik_limits(model, state, tasks, &lim, batch, steps, dT, nu, status, iters, active, s, slots, tau);
+}
+
 extern "C" {
+
+blf_status blf_fb_ik_solve_limits(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                                  const blf_ik_tasks* tasks, const blf_ik_hard* hard, const blf_ik_limits* limits,
+                                  int64_t batch, double* nu, int32_t* status, int32_t* iters, uint64_t* active,
+                                  void* stream)
+{
+    return ik_limits_call("blf_fb_ik_solve_limits", handle, model, state, tasks, hard, limits, batch, 0, 0.0, nu,
+                          status, iters, active, (hipStream_t)stream);
+}
+
+blf_status blf_fb_ik_integrate_limits(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                                      const blf_ik_tasks* tasks, const blf_ik_hard* hard,
+                                      const blf_ik_limits* limits, int64_t batch, int32_t steps, double dT,
+                                      double* nu, int32_t* status, int32_t* iters, uint64_t* active, void* stream)
+{
+    BLF_REQUIRE(steps >= 1, "blf_fb_ik_integrate_limits: steps=%d, must be >= 1", steps);
+    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_fb_ik_integrate_limits: dT=%g, must be finite and positive", dT);
+    return ik_limits_call("blf_fb_ik_integrate_limits", handle, model, state, tasks, hard, limits, batch, steps, dT,
+                          nu, status, iters, active, (hipStream_t)stream);
+}
 
 blf_status blf_fb_ik_solve(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
                            const blf_ik_tasks* tasks, int64_t batch, double* nu, int32_t* status,

@@ -149,7 +149,13 @@ blf_status launch_fb_frame_state(const blf_fb_model* md, const blf_fb_state* st,
 blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t, int64_t batch,
                         int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s,
                         uint32_t slots = 0, double tau = 0.0);
-size_t fb_ik_lds_bytes(int n, int K);
+// Section 12c: the same with the joints' velocity box (lim: device arrays, already validated;
+// max_iter > 0); slots may be 0.  iters [B] and active [B][2] may be null.
+blf_status launch_fb_ik_limits(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t,
+                               const blf_ik_limits* lim, int64_t batch, int32_t steps, double dT, double* nu,
+                               int32_t* status, int32_t* iters, uint64_t* active, hipStream_t s, uint32_t slots,
+                               double tau);
+size_t fb_ik_lds_bytes(int n, int K, bool limits = false);
 blf_status launch_posture_reference(const blf_posture_law* law, const double* com, const double* vrp,
                                     int64_t vstride, int64_t batch, double* qref, hipStream_t s);
 blf_status launch_fbk_euler(int n, double rho, double* pos, double* rot, double* joints,

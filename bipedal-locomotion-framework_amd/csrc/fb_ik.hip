@@ -14,6 +14,8 @@
 //      substitution, S = Y^T Y lane per row, its Cholesky with the relative pivot rule, lambda, and
 //      z - Y lambda into the backward substitution;
 //   5. nu to LDS (S.rhs()), from where the Euler step or the store takes it.
+// LIMITS kernels (section 12c, fb_ik_limits_kernel): an active-set iteration around steps 2b-5 on the
+// joints held at a bound of their velocity box, which step 3b eliminates from the system in place.
 // Built without the iterative-ILP scheduler of fb_dynamics.hip: LLVM's register allocator crashes
 // on the 54-row instantiation with it (the reason this kernel has a file of its own).
 #include "fb_common.h"
@@ -43,10 +45,11 @@ constexpr int kIkMc = 5;    // per-link mass moments: m | m c (odd stride)
 
 struct IkSmem {
     Smem S;   // the kinematics' compact layout; the IK's arrays follow it
-    int o_rows, o_wt, o_col, o_ts, o_mc, o_sp;
+    int o_rows, o_wt, o_col, o_ts, o_mc, o_sp, o_lim;
     int rs;   // task-row stride: the register row's width (columns past NV hold zeros)
     size_t total;
-    __host__ __device__ IkSmem(double* b, int n, int K, int nvmax) : S(b, n, 0, true)
+    // lim: the LIMITS kernels' block (section 12c); without it the layout is that of sections 12, 12b
+    __host__ __device__ IkSmem(double* b, int n, int K, int nvmax, bool lim = false) : S(b, n, 0, true)
     {
         const int NV = n + 6;
         rs = nvmax;
@@ -64,6 +67,8 @@ struct IkSmem {
         o_ts = take((size_t)kIkTs * (K > 0 ? K : 1));
         o_mc = take((size_t)kIkMc * (n + 1));
         o_sp = take(18 * (size_t)K + 6 + 2 * (size_t)n);   // set points: pose | twist | com | joints
+        // the velocity box lo n | up n, the value each fixed joint is held at n, the base position 3
+        o_lim = take(lim ? 3 * (size_t)n + 3 : 0);
         total = o;
     }
     __device__ __forceinline__ double* rows() const { return S.base + o_rows; }
@@ -72,16 +77,28 @@ struct IkSmem {
     __device__ __forceinline__ double* ts() const { return S.base + o_ts; }
     __device__ __forceinline__ double* mc() const { return S.base + o_mc; }
     __device__ __forceinline__ double* sp() const { return S.base + o_sp; }
+    __device__ __forceinline__ double* lo() const { return S.base + o_lim; }
+    __device__ __forceinline__ double* up(int n) const { return S.base + o_lim + n; }
+    __device__ __forceinline__ double* fx(int n) const { return S.base + o_lim + 2 * n; }
+    __device__ __forceinline__ double* pb(int n) const { return S.base + o_lim + 3 * n; }
 };
 
 // One solve for the robot whose state sits in S.st() (zero velocities | bp | bR | jp) and whose
 // set points sit in I.sp().  Leaves nu in S.rhs(); false if a pivot was not finite and positive.
 // HARD (section 12b): the rows of hd.slots hold exactly; hdep: a pivot of S failed its rule.
-template <int NVMAX, int HW, bool PRI, bool HARD>
+// LIMITS (section 12c) runs it in phases, PH: kPrep steps 1-2a once per state, kRows step 2b (again
+// after every solve: L and Y overwrite the rows), kSolve steps 3-5 with the joints of `wm` (bit j:
+// joint j, this lane's robot) fixed at I.fx(): they are eliminated from the system in place, a fixed
+// lane's row of H becoming e_i and its g_i the bound, a free lane's fixed columns moving to g_i.  The
+// hard rows' multipliers are then left in I.col() by table row.
+constexpr int kPrep = 1, kRows = 2, kSolve = 4;
+template <int NVMAX, int HW, bool PRI, bool HARD, bool LIMITS = false, int PH = kPrep | kRows | kSolve>
 __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const IkTasks& tk, const Topo& T,
-                                         const IkHard& hd, bool& hdep)
+                                         const IkHard& hd, bool& hdep, unsigned long long wm = 0ull)
 {
     static_assert(NVMAX <= HW, "a robot's rows must fit its lanes");
+    static_assert(LIMITS || PH == (kPrep | kRows | kSolve), "only the LIMITS kernels run in phases");
+    static_assert(HARD || !LIMITS, "the LIMITS kernels are built on the HARD ones (slots may be 0)");
     const Half<HW> H;
     const Smem& S = I.S;
     const int n = m.n, L = n + 1, NV = n + 6, MS = S.ms, K = tk.K;
@@ -93,9 +110,11 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
     const bool com = tk.cw != nullptr;
     const int M = 6 * K + (com ? 3 : 0);
     // 1. kinematics
-    fbd_kinematics<HW, PRI>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, jp, T);
+    if constexpr ((PH & kPrep) != 0) fbd_kinematics<HW, PRI>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, jp, T);
+    // (LIMITS: the base position, which 2b reads again after S's factor has gone over the link records)
+    if (LIMITS && (PH & kPrep) && lane < 3) I.pb(n)[lane] = S.link()[kP + lane];
     // 2a. lane per link: m_l and m_l c_l; lane per task: the frame's origin, the target twist, the link
-    if (com && lane < L) {
+    if ((PH & kPrep) && com && lane < L) {
         const double* k = S.link() + S.lrec * lane;
         const double* R = k + kR;
         const double* cl = m.com + 3 * lane;
@@ -105,7 +124,7 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
         for (int a = 0; a < 3; ++a)
             o[1 + a] = ms * (k[kP + a] + ((R[3 * a] * cl[0] + R[3 * a + 1] * cl[1]) + R[3 * a + 2] * cl[2]));
     }
-    if (lane < K) {
+    if ((PH & kPrep) && lane < K) {
         int f = tk.frame[lane];
         f = (f >= 0 && f < m.F) ? f : 0;   // out of range: the robot is BLF_IK_BAD_INPUT already
         const int l = m.flink[f];
@@ -126,8 +145,8 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
     wave_sync();
     // 2b. lane per column c: its motion (angular axis w about the point o, linear part u) and from
     //     it column c of every task row: u + w x (x - o) | w for a point x the column moves
-    {
-        const double* pB = S.link() + kP;
+    if constexpr ((PH & kRows) != 0) {
+        const double* pB = LIMITS ? I.pb(n) : S.link() + kP;
         const int j = lane >= 6 && lane < NV ? lane - 6 : 0;
         const bool jc = lane >= 6 && lane < NV;
         const bool pri = PRI && jc && m.jtype[j] == BLF_JOINT_PRISMATIC;
@@ -187,6 +206,7 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
         }
     }
     wave_sync();
+    if constexpr ((PH & kSolve) == 0) return true;
     // 3. row `lane` of H (its lower part; the entries above the diagonal are never read) and g
     double r[NVMAX], y = 0.0;
 #pragma unroll
@@ -208,6 +228,23 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
         y = lane >= 6 && lane < NV ? y + jw * sd : y;
 #pragma unroll
         for (int k = 0; k < NVMAX; ++k) r[k] = lane == k ? r[k] + dg : r[k];
+    }
+    // 3b. LIMITS: the fixed joints leave the system (selects over the unrolled columns: the sets of
+    //     a wavefront's two robots differ)
+    bool fixed = false;   // this lane's column is one of them
+    if constexpr (LIMITS) {
+        const double* fx = I.fx(n);
+        fixed = lane >= 6 && lane < NV && ((wm >> (lane - 6)) & 1ull);
+#pragma unroll
+        for (int j = 6; j < NVMAX; ++j) {
+            const bool fj = (wm >> (j - 6)) & 1ull;   // (no bit at or above n is ever set)
+            const double b = fx[j < NV ? j - 6 : 0];
+            y = fj ? y - r[j] * b : y;
+            r[j] = fj ? 0.0 : r[j];
+        }
+        y = fixed ? fx[fixed ? lane - 6 : 0] : y;
+#pragma unroll
+        for (int k = 0; k < NVMAX; ++k) r[k] = fixed ? (lane == k ? 1.0 : 0.0) : r[k];
     }
     // 4. Cholesky H = L L^T and the substitutions: fbd_eval's steps 8 and 9 (see there), with the
     //    pivot also required to be finite
@@ -275,9 +312,27 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
         const unsigned hm = hd.slots;   // wave-uniform
         const int mh = __builtin_popcount(hm);
         bool hok = mh <= NV;   // more hard rows than unknowns: dependent (and the factor would not fit)
-        if (hok) {
+        if constexpr (LIMITS) {
+            if (lane < kIkRows) I.col()[lane] = 0.0;   // the multipliers by table row (H's factor is done with it)
+            wave_sync();
+        }
+        if (hok && (!LIMITS || mh > 0)) {
             double* rows = I.rows();
             const int cl = lane < NVMAX ? lane : 0;
+            // LIMITS: the fixed columns leave the hard rows too, a_t . (fixed values) leaves their targets
+            double moved = 0.0;
+            if constexpr (LIMITS) {
+                int ow = 0, p = 0;
+#pragma unroll
+                for (int t = 0; t < kIkRows; ++t)
+                    if ((hm >> t) & 1u) {
+                        ow = lane == p ? t : ow;
+                        ++p;
+                    }
+                const double* ao = rows + ow * I.rs + 6;
+                const double* fx = I.fx(n);
+                for (int j = 0; j < n; ++j) moved = fma(ao[j], fx[j], moved);
+            }
             // (i) Y = L^-1 A_h^T: the forward substitution above on each hard row, three right-hand
             //     sides at a time (independent chains), y_t written back over row t
             constexpr int G = 3;
@@ -288,7 +343,7 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
                 for (int g = 0; g < G; ++g) {
                     t[g] = rest != 0u ? __builtin_ctz(rest) : -1;
                     rest = rest != 0u ? rest & (rest - 1u) : 0u;
-                    v[g] = t[g] >= 0 && lane < NV ? rows[t[g] * I.rs + cl] : 0.0;
+                    v[g] = t[g] >= 0 && lane < NV && !fixed ? rows[t[g] * I.rs + cl] : 0.0;
                 }
 #pragma unroll
                 for (int k = 0; k < NVMAX; ++k) {
@@ -331,7 +386,7 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
                     for (int t = 0; t < kIkRows; ++t)
                         if ((hm >> t) & 1u) sr[t] = fma(yi, rows[t * I.rs + c], sr[t]);
                 }
-                q = q - I.wt()[kIkRows + own];
+                q = q - (LIMITS ? I.wt()[kIkRows + own] - moved : I.wt()[kIkRows + own]);
             }
             double d0 = 0.0;   // S_ii before elimination
 #pragma unroll
@@ -390,6 +445,8 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
                     q = q - f * xk;
                 }
             }
+            if constexpr (LIMITS)
+                if (lane < mh) I.col()[own] = q;
             // (v) z - Y lambda
             {
                 int p = 0;
@@ -424,6 +481,263 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
     if (lane < NV) S.rhs()[lane] = y;
     wave_sync();
     return H.ballot(!ok) == 0ull;
+}
+
+// Robot q's state (zeros 6 + n | bp 3 | bR 9 | jp n into S.st()) and set points (I.sp()) into LDS;
+// true if a set point is not finite or a frame index is out of range.  fb_ik_kernel's staging and
+// store, for fb_ik_limits_kernel: fb_ik_kernel keeps its own text, since calling these from it moves
+// the register allocation of its eight instantiations (same instructions, other registers and order).
+template <int HW>
+__device__ __forceinline__ bool ik_stage(const Model& m, const IkSmem& I, const blf_fb_state& st, const IkTasks& tk,
+                                         int64_t q)
+{
+    const Half<HW> H;
+    const int n = m.n, K = tk.K, lane = H.hl;
+    double* loc = I.S.st();
+    for (int i = lane; i < 18 + 2 * n; i += HW) {
+        double v = 0.0;
+        if (i < 6 + n) v = 0.0;
+        else if (i < 9 + n) v = st.base_pos[3 * q + (i - 6 - n)];
+        else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
+        loc[i] = v;
+    }
+    bool fin = true;
+    for (int i = lane; i < 18 * K + 6 + 2 * n; i += HW) {
+        double v = 0.0;
+        if (i < 12 * K) v = tk.pose[q * 12 * K + i];
+        else if (i < 18 * K) v = tk.twist ? tk.twist[q * 6 * K + (i - 12 * K)] : 0.0;
+        else if (i < 18 * K + 3) v = tk.cw ? tk.cpos[3 * q + (i - 18 * K)] : 0.0;
+        else if (i < 18 * K + 6) v = tk.cw && tk.cvel ? tk.cvel[3 * q + (i - 18 * K - 3)] : 0.0;
+        else if (i < 18 * K + 6 + n) v = tk.jpos[(int64_t)n * q + (i - 18 * K - 6)];
+        else v = tk.jvel ? tk.jvel[(int64_t)n * q + (i - 18 * K - 6 - n)] : 0.0;
+        I.sp()[i] = v;
+        fin = fin && so3_finite(v);
+    }
+    bool fbad = false;   // the frame indices are shared by the batch
+    for (int k = 0; k < K; ++k) {
+        const int f = tk.frame[k];
+        fbad = fbad || f < 0 || f >= m.F;
+    }
+    const bool spbad = fbad || H.ballot(!fin) != 0ull;
+    wave_sync();
+    return spbad;
+}
+
+// Robot q's results: nu (NaN unless its status is OK), after an integration the state, and the status.
+template <int HW>
+__device__ __forceinline__ void ik_store(const Model& m, const IkSmem& I, const blf_fb_state& st, int32_t steps,
+                                         double* __restrict__ nu, int32_t* __restrict__ status, int64_t q, int stat)
+{
+    const Half<HW> H;
+    const Smem& S = I.S;
+    const int n = m.n, NV = n + 6, lane = H.hl;
+    const double* loc = S.st();
+    const double nan = __builtin_nan("");
+    for (int c = lane; c < NV; c += HW) {
+        const double v = stat == BLF_IK_OK ? S.rhs()[c] : nan;
+        if (nu) nu[(int64_t)NV * q + c] = v;
+        if (steps > 0) {
+            if (c < 6) st.base_vel[6 * q + c] = v;
+            else st.joint_vel[(int64_t)n * q + (c - 6)] = v;
+        }
+    }
+    if (steps > 0)
+        for (int i = lane; i < 12 + n; i += HW) {
+            const double v = loc[6 + n + i];
+            if (i < 3) st.base_pos[3 * q + i] = v;
+            else if (i < 12) st.base_rot[9 * q + (i - 3)] = v;
+            else st.joint_pos[(int64_t)n * q + (i - 12)] = v;
+        }
+    if (status && lane == 0) status[q] = stat;
+}
+
+// Section 12c's rho = g_soft - H_soft nu - A_h^T lambda of this lane's column (0 on the base columns),
+// from the rebuilt task rows, nu in S.rhs() and the multipliers in I.col(): lane per task row t,
+// e_t = w_t (t_t - a_t . nu) - lambda_t (over I.col(); each lane starts its dot at its own column, so
+// the lanes' reads fall on different banks), then lane per column sum_t a_tc e_t + jw (sdot* - nu).
+template <int HW>
+__device__ __forceinline__ double ik_rho(const Model& m, const IkSmem& I, const IkTasks& tk)
+{
+    const Half<HW> H;
+    const Smem& S = I.S;
+    const int n = m.n, NV = n + 6, K = tk.K, lane = H.hl;
+    const int M = 6 * K + (tk.cw != nullptr ? 3 : 0);
+    const double* rows = I.rows();
+    const double* x = S.rhs();
+    double* e = I.col();
+    if (lane < M) {
+        const double w = I.wt()[lane];
+        const double* a = rows + lane * I.rs;
+        double d = 0.0;
+        int c = lane % NV;
+        for (int k = 0; k < NV; ++k) {
+            d = fma(a[c], x[c], d);
+            c = c + 1 == NV ? 0 : c + 1;
+        }
+        const double ev = w != 0.0 ? w * (I.wt()[kIkRows + lane] - d) - e[lane] : -e[lane];
+        e[lane] = ev;   // (the lane's own slot)
+    }
+    wave_sync();
+    double rho = 0.0;
+    if (lane >= 6 && lane < NV) {
+        const int j = lane - 6;
+        for (int t = 0; t < M; ++t) rho = fma(rows[t * I.rs + lane], e[t], rho);
+        const double* sp = I.sp();
+        const double* jp = S.st() + 18 + n;
+        const double sd = sp[18 * K + 6 + n + j] + tk.jkp[j] * (sp[18 * K + 6 + j] - jp[j]);
+        rho = rho + tk.jw[j] * (sd - x[lane]);
+    }
+    wave_sync();
+    return rho;
+}
+
+// Section 12c as the kernel takes it (shared by the batch).
+struct IkLimits {
+    const double *lower, *upper, *klim, *vmax;
+    double sampling;
+    int max_iter;
+};
+
+// blf_fb_ik_solve_limits (steps == 0) and blf_fb_ik_integrate_limits: fb_ik_kernel with section 12c's
+// active-set iteration around the solve.  The working set (two masks), the mode and the counters
+// are per robot (the same in every lane of its half); the iteration's trip count is wave-uniform by
+// a ballot, a finished robot repeating its last solve unchanged while its neighbour goes on.
+template <int NVMAX, int HW, bool PRI>
+__global__ __launch_bounds__(64) void fb_ik_limits_kernel(Model m, blf_fb_state st, IkTasks tk, int32_t steps,
+                                                          double dT, double* __restrict__ nu,
+                                                          int32_t* __restrict__ status, int64_t batch, IkHard hd,
+                                                          IkLimits lp, int32_t* __restrict__ iters_out,
+                                                          unsigned long long* __restrict__ active_out)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const Half<HW> H;
+    const int n = m.n, NV = n + 6, K = tk.K;
+    const IkSmem I(smem + H.half * IkSmem(nullptr, n, K, NVMAX, true).total, n, K, NVMAX, true);
+    const Smem& S = I.S;
+    const int lane = H.hl;
+    constexpr int per = kWave / HW;   // robots per wavefront
+    const Topo T = build_topo<HW>(m, S);
+    const int64_t i0 = (int64_t)blockIdx.x * per + H.half;
+    const bool active = i0 < batch;   // see fbd_dynamics_kernel
+    const int64_t q = active ? i0 : batch - 1;
+    double* loc = S.st();
+    double* dR = loc + 18 + 2 * n;
+    const bool spbad = ik_stage<HW>(m, I, st, tk, q);
+    const bool jc = lane >= 6 && lane < NV;   // this lane's column is joint j
+    const int j = jc ? lane - 6 : 0;
+    int stat = BLF_IK_OK, total = 0;
+    unsigned long long wl = 0ull, wu = 0ull;   // joints held at their lower / upper bound
+    const int iters = steps > 0 ? steps : 1;
+    for (int it = 0; it < iters; ++it) {
+        const bool alive = stat == BLF_IK_OK;
+        if (!__ballot(alive)) break;
+        bool sfin = true;
+        for (int i = lane; i < 12 + n; i += HW) sfin = sfin && so3_finite(loc[6 + n + i]);
+        const bool bad = spbad || H.ballot(!sfin) != 0ull;
+        stat = alive && bad ? BLF_IK_BAD_INPUT : stat;
+        // the box at this state
+        if (lane < n) {
+            const double s = loc[18 + n + lane], kl = lp.klim[lane];
+            const double vm = lp.vmax ? lp.vmax[lane] : __builtin_inf();
+            const double a = kl * (lp.lower[lane] - s) / lp.sampling, b = kl * (lp.upper[lane] - s) / lp.sampling;
+            I.lo()[lane] = fmin(fmax(a, -vm), vm);
+            I.up(n)[lane] = fmin(fmax(b, -vm), vm);
+            I.fx(n)[lane] = 0.0;
+        }
+        bool hdep = false;
+        ik_solve<NVMAX, HW, PRI, true, true, kPrep | kRows>(m, I, tk, T, hd, hdep);
+        bool done = stat != BLF_IK_OK, block = true;
+        int best = 0x7fffffff, stall = 0, nit = 0;
+        unsigned long long pl = 0ull, pu = 0ull;   // the set before the last block update
+        wl = 0ull;
+        wu = 0ull;
+        while (__ballot(!done)) {
+            const unsigned long long wm = wl | wu;
+            const bool ok = ik_solve<NVMAX, HW, PRI, true, true, kSolve>(m, I, tk, T, hd, hdep, wm);
+            nit = done ? nit : nit + 1;
+            const int s1 = !ok ? BLF_IK_NOT_POSITIVE : hdep && wm == 0ull ? BLF_IK_HARD_DEPENDENT : BLF_IK_OK;
+            stat = done ? stat : s1;
+            done = done || s1 != BLF_IK_OK;
+            // a set that made the hard rows dependent: back to the one before it, one joint at a time from here
+            const bool back = !done && hdep;
+            if (back && !block) stat = BLF_IK_LIMITS_UNRESOLVED;
+            done = done || (back && !block);
+            wl = back ? pl : wl;
+            wu = back ? pu : wu;
+            block = back ? false : block;
+            // free joints outside their box
+            const double v = S.rhs()[jc ? lane : 0];
+            const double lo = I.lo()[j], up = I.up(n)[j];
+            const bool held = (wm >> j) & 1ull;
+            const bool go = !done && !back;
+            const unsigned long long vl = H.ballot(go && jc && !held && v < lo) >> 6;
+            const unsigned long long vu = H.ballot(go && jc && !held && v > up) >> 6;
+            unsigned long long rl = 0ull, ru = 0ull;   // held joints whose rho points into the box
+            if (__ballot(!done)) ik_solve<NVMAX, HW, PRI, true, true, kRows>(m, I, tk, T, hd, hdep);
+            if (__ballot(go && wm != 0ull)) {
+                const double rho = ik_rho<HW>(m, I, tk);
+                rl = H.ballot(go && jc && ((wl >> j) & 1ull) && rho > 0.0) >> 6;
+                ru = H.ballot(go && jc && ((wu >> j) & 1ull) && rho < 0.0) >> 6;
+            }
+            const int ninf = __builtin_popcountll(vl | vu | rl | ru);
+            done = done || (go && ninf == 0);
+            const bool more = !done && go;
+            if (more && nit >= lp.max_iter) stat = BLF_IK_LIMITS_UNRESOLVED;
+            if (back && !done && nit >= lp.max_iter) stat = BLF_IK_LIMITS_UNRESOLVED;
+            done = done || stat != BLF_IK_OK;
+            const bool upd = more && !done;
+            if (upd && block) {
+                stall = ninf < best ? 0 : stall + 1;
+                best = ninf < best ? ninf : best;
+                block = stall < 8;
+            }
+            if (upd && block) {
+                pl = wl;
+                pu = wu;
+                wl = (wl & ~rl) | vl;
+                wu = (wu & ~ru) | vu;
+            }
+            if (__ballot(upd && !block)) {
+                // one joint: the most violated free one (the lowest index among equals), else the
+                // lowest-index held one of the wrong sign
+                const double mag = v < lo ? lo - v : v - up;
+                double bm = 0.0;
+                int bj = -1;
+                for (int c = 6; c < NV; ++c) {
+                    const double mc = H.bcast_k(mag, c);
+                    const bool in = ((vl | vu) >> (c - 6)) & 1ull;
+                    bj = in && mc > bm ? c - 6 : bj;
+                    bm = in && mc > bm ? mc : bm;
+                }
+                const unsigned long long rr = rl | ru;
+                const unsigned long long pick = bj >= 0 ? 1ull << bj : rr & (~rr + 1ull);
+                if (upd && !block) {
+                    wl = bj >= 0 ? wl | (pick & vl) : wl & ~pick;
+                    wu = bj >= 0 ? wu | (pick & vu) : wu & ~pick;
+                }
+            }
+            if (jc) I.fx(n)[j] = ((wl >> j) & 1ull) ? lo : ((wu >> j) & 1ull) ? up : 0.0;
+            wave_sync();
+        }
+        total += nit;
+        if (steps > 0) {
+            const bool step = stat == BLF_IK_OK;
+            if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, S.rhs() + 3, dR);
+            wave_sync();
+            if (step)
+                for (int i = lane; i < 12 + n; i += HW) {
+                    if (i < 3) loc[6 + n + i] = loc[6 + n + i] + S.rhs()[i] * dT;
+                    else if (i < 12) loc[6 + n + i] = loc[6 + n + i] + dR[i - 3] * dT;
+                    else loc[18 + n + (i - 12)] = loc[18 + n + (i - 12)] + S.rhs()[6 + (i - 12)] * dT;
+                }
+            wave_sync();
+        }
+    }
+    if (!active) return;
+    ik_store<HW>(m, I, st, steps, nu, status, q, stat);
+    if (iters_out && lane == 0) iters_out[q] = total;
+    if (active_out && lane < 2) active_out[2 * q + lane] = stat != BLF_IK_OK ? 0ull : lane == 0 ? wl : wu;
 }
 
 // blf_fb_ik_solve (steps == 0) and blf_fb_ik_integrate (steps >= 1): the set points staged in LDS
@@ -526,18 +840,14 @@ __global__ __launch_bounds__(64) void fb_ik_kernel(Model m, blf_fb_state st, IkT
 // Two robots per wavefront while a robot's rows fit half of one (n + 6 <= 32), as the dynamics
 // kernels: at n = 24, B = 16 384 the solve takes 0.431 ms with two robots per wavefront and 0.965 ms
 // with one, and 20 fused steps 6.29 against 15.24 ms (profiles/ik_bench.log).
-size_t fb_ik_lds_bytes(int n, int K)
+size_t fb_ik_lds_bytes(int n, int K, bool limits)
 {
-    return n + 6 <= 32 ? 2 * sizeof(double) * IkSmem(nullptr, n, K, 32).total
-                       : sizeof(double) * IkSmem(nullptr, n, K, BLF_FBD_MAX_DOFS + 6).total;
+    return n + 6 <= 32 ? 2 * sizeof(double) * IkSmem(nullptr, n, K, 32, limits).total
+                       : sizeof(double) * IkSmem(nullptr, n, K, BLF_FBD_MAX_DOFS + 6, limits).total;
 }
 
-// slots == 0: the soft kernels (section 12); otherwise the HARD ones (section 12b)
-blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t, int64_t batch,
-                        int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s,
-                        uint32_t slots, double tau)
+static IkTasks to_tasks(const blf_ik_tasks* t)
 {
-    if (batch == 0) return BLF_OK;
     IkTasks tk;
     tk.K = t->nse3;
     tk.frame = t->frame;
@@ -554,6 +864,16 @@ blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const bl
     tk.jvel = t->joint_vel;
     tk.ckp = t->com_kp;
     tk.damp = t->base_damping;
+    return tk;
+}
+
+// slots == 0: the soft kernels (section 12); otherwise the HARD ones (section 12b)
+blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t, int64_t batch,
+                        int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s,
+                        uint32_t slots, double tau)
+{
+    if (batch == 0) return BLF_OK;
+    const IkTasks tk = to_tasks(t);
     const bool pri = md->joint_type != nullptr;
     const size_t lds = fb_ik_lds_bytes(md->ndof, tk.K);
     const IkHard hd{slots, tau};
@@ -570,6 +890,31 @@ blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const bl
                            status, batch, hd);
     }
     return check_hip(hipGetLastError(), "fb_ik_kernel launch");
+}
+
+blf_status launch_fb_ik_limits(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t,
+                               const blf_ik_limits* lim, int64_t batch, int32_t steps, double dT, double* nu,
+                               int32_t* status, int32_t* iters, uint64_t* active, hipStream_t s, uint32_t slots,
+                               double tau)
+{
+    if (batch == 0) return BLF_OK;
+    const IkTasks tk = to_tasks(t);
+    const bool pri = md->joint_type != nullptr;
+    const size_t lds = fb_ik_lds_bytes(md->ndof, tk.K, true);
+    const IkHard hd{slots, tau};
+    const IkLimits lp{lim->pos_lower, lim->pos_upper, lim->klim, lim->vel_max, lim->sampling_time, lim->max_iter};
+    unsigned long long* act = reinterpret_cast<unsigned long long*>(active);
+    constexpr int NW = BLF_FBD_MAX_DOFS + 6;
+    if (md->ndof + 6 <= 32) {
+        auto kern = pri ? fb_ik_limits_kernel<32, 32, true> : fb_ik_limits_kernel<32, 32, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), lds, s, to_model(md), *st, tk,
+                           steps, dT, nu, status, batch, hd, lp, iters, act);
+    } else {
+        auto kern = pri ? fb_ik_limits_kernel<NW, kWave, true> : fb_ik_limits_kernel<NW, kWave, false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, tk, steps, dT, nu,
+                           status, batch, hd, lp, iters, act);
+    }
+    return check_hip(hipGetLastError(), "fb_ik_limits_kernel launch");
 }
 
 }  // namespace blf

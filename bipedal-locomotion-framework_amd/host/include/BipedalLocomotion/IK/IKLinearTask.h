@@ -1,8 +1,8 @@
 /**
  * @file IKLinearTask.h
  * Base of the inverse-kinematics tasks QPInverseKinematics accepts (upstream's IK::IKLinearTask).
- * Upstream's task is a generic linear row block A nu = b evaluated through iDynTree; here the three
- * task kinds the device kernel forms itself (include/blf/blf_c.h section 12) are the whole set, so
+ * Upstream's task is a generic linear row block A nu = b evaluated through iDynTree; here the task
+ * kinds the device kernel forms itself (include/blf/blf_c.h sections 12 and 12c) are the whole set, so
  * the base only carries the kind and the parameter handling.
  */
 #ifndef BLF_BIPEDAL_LOCOMOTION_IK_LINEAR_TASK_H
@@ -24,7 +24,8 @@ public:
     {
         SE3,
         CoM,
-        JointTracking
+        JointTracking,
+        JointLimits
     };
     virtual ~IKLinearTask() = default;
     virtual Kind kind() const = 0;

@@ -4,14 +4,19 @@
  * advance() solves for the generalized velocity nu = (base mixed twist, joint velocities) that
  * minimises the weighted task errors at the robot state, on the device (blf_fb_ik_solve,
  * include/blf/blf_c.h section 12), subject to the hard (priority 0) tasks holding exactly
- * (blf_fb_ik_solve_hard, section 12b).  Integrating that velocity with
+ * (blf_fb_ik_solve_hard, section 12b) and to the joint limits of a JointLimitsTask
+ * (blf_fb_ik_solve_limits, section 12c).  Integrating that velocity with
  * ForwardEuler<FloatingBaseSystemKinematics> and feeding the state back with setRobotState() is
  * upstream's IntegrationBasedIK loop; blf_fb_ik_integrate(_hard) runs the same loop in one launch.
  *
  * Differences from upstream a user can notice: priority 0 (hard) is for SE3Task and CoMTask only
  * and always covers every row of the task (a mask over single rows is the C ABI's); hard tasks that
  * are linearly dependent, conflicting or more than 6 + n rows make advance() return false instead
- * of leaving the choice to a QP solver; there are no inequality tasks and no priorities above 1; at
+ * of leaving the choice to a QP solver; the only inequality task is JointLimitsTask (priority 0,
+ * once), solved by section 12c's active-set iteration, which is not a complete QP solver: where the
+ * limits contradict the hard tasks, and in rare barely feasible cases, advance() returns false
+ * (BLF_IK_LIMITS_UNRESOLVED) where a QP solver would report infeasibility or find the point; there
+ * are no priorities above 1; at
  * most BLF_IK_MAX_SE3_TASKS SE3 tasks, one CoM task and one joint
  * tracking task, which is required and weighted (it makes the problem positive definite); the robot is a
  * blf::RobotModel set with setRobotModel() (no iDynTree KinDynComputations) and its state is given
@@ -29,6 +34,7 @@
 
 #include <BipedalLocomotion/IK/CoMTask.h>
 #include <BipedalLocomotion/IK/IKLinearTask.h>
+#include <BipedalLocomotion/IK/JointLimitsTask.h>
 #include <BipedalLocomotion/IK/JointTrackingTask.h>
 #include <BipedalLocomotion/IK/SE3Task.h>
 #include <BipedalLocomotion/System/Advanceable.h>
@@ -69,7 +75,8 @@ public:
      * Add a task.  Priority 1 (weighted): weight holds one entry per task row (SE3: 6, linear xyz
      * then angular xyz; CoM: 3; joint tracking: one per joint, > 0), each finite and >= 0.
      * Priority 0 (hard: every row of the task holds exactly): an SE3Task or a CoMTask, with an
-     * empty weight.  False with a "[QPInverseKinematics::addTask] ..." line for any other
+     * empty weight; or the JointLimitsTask (priority 0 only, once, empty weight).
+     * False with a "[QPInverseKinematics::addTask] ..." line for any other
      * priority, priority 0 with a weight or for a JointTrackingTask, a null task, a duplicate name,
      * a wrong weight, a fifth SE3 task, a second CoM or joint tracking task, or after finalize().
      */
@@ -78,13 +85,16 @@ public:
 
     std::vector<std::string> getTaskNames() const;
 
-    /** Resolve the frames and fix the task set; false without a model or with an unknown frame. */
+    /** Resolve the frames and fix the task set; false without a model or with an unknown frame, or
+     * when the JointLimitsTask's sizes do not match the model or it asks for the model's limits
+     * ("use_model_limits") and the model has none. */
     bool finalize();
 
     /** Solve at the robot state with the tasks' current set points.  False before finalize() or
      * setRobotState(), without a joint tracking task, when a task has no set point or a wrong size,
-     * or when the device reports a failed solve, dependent hard tasks (BLF_IK_HARD_DEPENDENT)
-     * among them (the state is then invalid). */
+     * or when the device reports a failed solve, dependent hard tasks (BLF_IK_HARD_DEPENDENT) and
+     * joint limits the iteration could not resolve (BLF_IK_LIMITS_UNRESOLVED) among them (the
+     * state is then invalid). */
     bool advance() final;
     const IntegrationBasedIKState& get() const final { return m_state; }
     bool isValid() const final { return m_isValid; }
@@ -95,6 +105,8 @@ public:
     const blf_fb_state& deviceState() const { return m_cState; }
     const blf_ik_tasks& deviceTasks() const { return m_cTasks; }
     const blf_ik_hard& deviceHard() const { return m_cHard; }
+    /** The limits of the last advance(); every pointer is null without a JointLimitsTask. */
+    const blf_ik_limits& deviceLimits() const { return m_cLimits; }
 
     /** Section 12b's mask of the hard tasks added so far: bits 6k..6k+5 for the k-th SE3 task (in
      * the order they were added) when it is hard, bits 24..26 for a hard CoM task. */
@@ -110,7 +122,8 @@ private:
     };
     std::vector<Entry> m_tasks;
     std::vector<int32_t> m_frames;
-    int m_comTask{-1}, m_jointTask{-1};
+    int m_comTask{-1}, m_jointTask{-1}, m_limitsTask{-1};
+    std::vector<double> m_limits;   // finalize(): pos_lower n | pos_upper n | klim n | vel_max n (or none)
     bool m_isFinalized{false}, m_hasModel{false}, m_hasState{false}, m_isValid{false};
     double m_baseDamping{0.0}, m_hardWeight{1.0};
     blf::RobotModel m_model;
@@ -127,6 +140,8 @@ private:
     blf_fb_state m_cState{};
     blf_ik_tasks m_cTasks{};
     blf_ik_hard m_cHard{};
+    blf_ik_limits m_cLimits{};
+    blf::DeviceBuffer<double> m_dLimits;
 };
 
 } // namespace IK

@@ -54,6 +54,10 @@ struct RobotModel
     /** [n] or empty (every joint revolute): BLF_JOINT_REVOLUTE / BLF_JOINT_PRISMATIC (the child
      *  link slides along the joint axis by q, URDF "prismatic"). */
     std::vector<int32_t> jointType;
+    /** [n] or empty (no limits): the joints' position range, -inf / +inf where a side has none, and
+     *  their velocity limit (+inf: none).  blf::loadUrdf fills them from <limit>; the IK's
+     *  JointLimitsTask reads them with "use_model_limits".  The dynamics do not use them. */
+    std::vector<double> jointLower, jointUpper, jointVelocityLimit;
 };
 
 /** The model with every joint marked in model.fixedJoint removed and its child link merged into

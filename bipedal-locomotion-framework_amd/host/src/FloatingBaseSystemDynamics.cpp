@@ -40,7 +40,10 @@ bool blf::fixedJointMergeable(const RobotModel& in)
         || in.jointRotation.size() != 9 * n0 || in.jointAxis.size() != 3 * n0
         || in.linkMass.size() != n0 + 1 || in.linkCom.size() != 3 * (n0 + 1)
         || in.linkInertia.size() != 9 * (n0 + 1) || in.framePose.size() != 12 * in.frameLink.size()
-        || (!in.jointType.empty() && in.jointType.size() != n0))
+        || (!in.jointType.empty() && in.jointType.size() != n0)
+        || (!in.jointLower.empty() && in.jointLower.size() != n0)
+        || (!in.jointUpper.empty() && in.jointUpper.size() != n0)
+        || (!in.jointVelocityLimit.empty() && in.jointVelocityLimit.size() != n0))
         return false;
     // the merge re-indexes joints and links assuming topological order (a joint's parent link
     // precedes its child: parent[j] <= j), and moves frames by link index
@@ -123,6 +126,8 @@ blf::RobotModel blf::reduceFixedJoints(const RobotModel& in)
         m.jointRotation.erase(m.jointRotation.begin() + 9 * j, m.jointRotation.begin() + 9 * j + 9);
         m.jointAxis.erase(m.jointAxis.begin() + 3 * j, m.jointAxis.begin() + 3 * j + 3);
         if (m.jointType.size() == static_cast<std::size_t>(m.ndof)) m.jointType.erase(m.jointType.begin() + j);
+        for (std::vector<double>* lim : {&m.jointLower, &m.jointUpper, &m.jointVelocityLimit})
+            if (lim->size() == static_cast<std::size_t>(m.ndof)) lim->erase(lim->begin() + j);
         m.linkMass.erase(m.linkMass.begin() + c);
         m.linkCom.erase(m.linkCom.begin() + 3 * c, m.linkCom.begin() + 3 * c + 3);
         m.linkInertia.erase(m.linkInertia.begin() + 9 * c, m.linkInertia.begin() + 9 * c + 9);

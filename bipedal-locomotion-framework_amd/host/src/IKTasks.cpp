@@ -8,6 +8,7 @@
 #include <iostream>
 
 #include <BipedalLocomotion/IK/CoMTask.h>
+#include <BipedalLocomotion/IK/JointLimitsTask.h>
 #include <BipedalLocomotion/IK/JointTrackingTask.h>
 #include <BipedalLocomotion/IK/SE3Task.h>
 
@@ -173,5 +174,85 @@ bool JointTrackingTask::setSetPoint(const blf::VectorXd& jointPosition, const bl
     m_position = jointPosition;
     m_velocity = jointVelocity;
     m_hasSetPoint = true;
+    return true;
+}
+
+bool JointLimitsTask::initialize(std::weak_ptr<IParametersHandler> handlerWeak)
+{
+    constexpr const char* where = "[JointLimitsTask::initialize] ";
+    m_isInitialized = false;
+    auto handler = handlerWeak.lock();
+    if (handler == nullptr)
+    {
+        std::cerr << where << "The parameters handler no longer exists." << std::endl;
+        return false;
+    }
+    std::vector<double> klim, lower, upper, velocity;
+    double samplingTime = 0.0;
+    bool useModel = false;
+    if (!handler->getParameter("klim", klim) || klim.empty())
+    {
+        std::cerr << where << "The parameter klim is missing." << std::endl;
+        return false;
+    }
+    for (const double k : klim)
+        if (!(k > 0.0 && k <= 1.0))
+        {
+            std::cerr << where << "The gains klim must be in (0, 1]." << std::endl;
+            return false;
+        }
+    if (!handler->getParameter("sampling_time", samplingTime) || !std::isfinite(samplingTime) || samplingTime <= 0.0)
+    {
+        std::cerr << where << "The parameter sampling_time is missing or not a positive number." << std::endl;
+        return false;
+    }
+    if (!handler->getParameter("use_model_limits", useModel))
+    {
+        std::cerr << where << "The parameter use_model_limits is missing." << std::endl;
+        return false;
+    }
+    if (!useModel)
+    {
+        if (!handler->getParameter("lower_limits", lower) || !handler->getParameter("upper_limits", upper))
+        {
+            std::cerr << where << "The parameters lower_limits and upper_limits are required without "
+                                  "use_model_limits."
+                      << std::endl;
+            return false;
+        }
+        if (lower.size() != klim.size() || upper.size() != klim.size())
+        {
+            std::cerr << where << "Wrong size of the vectors: " << klim.size() << " gains, " << lower.size()
+                      << " lower and " << upper.size() << " upper limits." << std::endl;
+            return false;
+        }
+        for (std::size_t j = 0; j < klim.size(); ++j)
+            if (!(lower[j] <= upper[j]) || lower[j] == HUGE_VAL || upper[j] == -HUGE_VAL)
+            {
+                std::cerr << where << "Every lower limit must be at most its upper limit." << std::endl;
+                return false;
+            }
+    }
+    if (handler->getParameter("velocity_limits", velocity))
+    {
+        if (velocity.size() != klim.size())
+        {
+            std::cerr << where << "The velocity_limits must have one entry per joint." << std::endl;
+            return false;
+        }
+        for (const double v : velocity)
+            if (!(v > 0.0))
+            {
+                std::cerr << where << "The velocity_limits must be positive." << std::endl;
+                return false;
+            }
+    }
+    m_klim = klim;
+    m_lower = lower;
+    m_upper = upper;
+    m_velocity = velocity;
+    m_samplingTime = samplingTime;
+    m_useModelLimits = useModel;
+    m_isInitialized = true;
     return true;
 }

@@ -1,8 +1,8 @@
 /**
  * @file QPInverseKinematics.cpp
  * The task bookkeeping of IK::QPInverseKinematics on the host; every advance() is one
- * blf_fb_ik_solve, or with hard tasks blf_fb_ik_solve_hard, for one robot (include/blf/blf_c.h
- * sections 12 and 12b).
+ * blf_fb_ik_solve, with hard tasks blf_fb_ik_solve_hard, with a JointLimitsTask
+ * blf_fb_ik_solve_limits, for one robot (include/blf/blf_c.h sections 12, 12b and 12c).
  */
 #include <algorithm>
 #include <cmath>
@@ -65,7 +65,9 @@ bool QPInverseKinematics::setRobotModel(const blf::RobotModel& fullModel,
         || model.jointAxis.size() != 3 * n || model.linkMass.size() != n + 1
         || model.linkCom.size() != 3 * (n + 1) || model.linkInertia.size() != 9 * (n + 1)
         || model.framePose.size() != 12 * F || (!model.jointType.empty() && model.jointType.size() != n)
-        || (!frameNames.empty() && frameNames.size() != F))
+        || (!frameNames.empty() && frameNames.size() != F)
+        || model.jointLower.size() != model.jointUpper.size()
+        || (!model.jointLower.empty() && model.jointLower.size() != n))
     {
         std::cerr << where << "Corrupted robot model." << std::endl;
         return false;
@@ -146,6 +148,13 @@ bool QPInverseKinematics::addTask(std::shared_ptr<IKLinearTask> task, const std:
         return false;
     }
     const bool hard = priority == 0;
+    if (task->kind() == IKLinearTask::Kind::JointLimits && (!hard || m_limitsTask >= 0))
+    {
+        std::cerr << where << "The task " << taskName << " is a joint limits task: it is accepted at priority 0 "
+                     "only, and once."
+                  << std::endl;
+        return false;
+    }
     if (hard && weight.size() != 0)
     {
         std::cerr << where << "The task " << taskName << " has priority 0: a hard task takes no weight."
@@ -166,6 +175,12 @@ bool QPInverseKinematics::addTask(std::shared_ptr<IKLinearTask> task, const std:
             return false;
         }
     const IKLinearTask::Kind kind = task->kind();
+    if (kind == IKLinearTask::Kind::JointLimits)
+    {
+        m_limitsTask = static_cast<int>(m_tasks.size());
+        m_tasks.push_back(Entry{taskName, std::move(task), {}, true});
+        return true;
+    }
     std::size_t se3 = 0;
     for (const Entry& e : m_tasks) se3 += e.task->kind() == IKLinearTask::Kind::SE3;
     if (kind == IKLinearTask::Kind::SE3 && se3 >= BLF_IK_MAX_SE3_TASKS)
@@ -219,7 +234,7 @@ uint32_t QPInverseKinematics::hardRows() const
     {
         if (e.task->kind() == IKLinearTask::Kind::SE3)
         {
-            if (e.hard) rows |= 0x3fu << (6 * k);
+            if (e.hard) rows |= 0x3fu << (6 * k);   // (the joint limits task has no rows)
             ++k;
         }
         else if (e.task->kind() == IKLinearTask::Kind::CoM && e.hard)
@@ -267,6 +282,31 @@ bool QPInverseKinematics::finalize()
         std::cerr << where << "The joint tracking task's weight must have one entry per joint." << std::endl;
         return false;
     }
+    std::vector<double> limits;
+    if (m_limitsTask >= 0)
+    {
+        const auto& lt = static_cast<const JointLimitsTask&>(*m_tasks[m_limitsTask].task);
+        const std::size_t n = static_cast<std::size_t>(m_model.ndof);
+        if (!lt.isValid() || lt.klim().size() != n)
+        {
+            std::cerr << where << "The joint limits task " << m_tasks[m_limitsTask].name << " is not initialized "
+                      << "or has " << lt.klim().size() << " joints, the model " << n << "." << std::endl;
+            return false;
+        }
+        if (lt.useModelLimits() && m_model.jointLower.size() != n)
+        {
+            std::cerr << where << "The joint limits task asks for the model's limits and the model has none."
+                      << std::endl;
+            return false;
+        }
+        const std::vector<double>& lo = lt.useModelLimits() ? m_model.jointLower : lt.lowerLimits();
+        const std::vector<double>& up = lt.useModelLimits() ? m_model.jointUpper : lt.upperLimits();
+        limits.insert(limits.end(), lo.begin(), lo.end());
+        limits.insert(limits.end(), up.begin(), up.end());
+        limits.insert(limits.end(), lt.klim().begin(), lt.klim().end());
+        limits.insert(limits.end(), lt.velocityLimits().begin(), lt.velocityLimits().end());
+    }
+    m_limits = limits;
     m_frames = frames;
     m_isFinalized = true;
     return true;
@@ -395,10 +435,24 @@ bool QPInverseKinematics::advance()
     int32_t* status = m_dInt.data() + K;
     m_cHard = blf_ik_hard{};
     m_cHard.rows = hardRows();
-    const blf_status called = m_cHard.rows != 0
-                                  ? blf_fb_ik_solve_hard(h, &m_cModel, &m_cState, &m_cTasks, &m_cHard, 1, d, status,
-                                                         nullptr)
-                                  : blf_fb_ik_solve(h, &m_cModel, &m_cState, &m_cTasks, 1, d, status, nullptr);
+    m_cLimits = blf_ik_limits{};
+    if (m_limitsTask >= 0)
+    {
+        if (!m_dLimits.upload(m_limits)) return false;
+        const auto& lt = static_cast<const JointLimitsTask&>(*m_tasks[m_limitsTask].task);
+        m_cLimits.pos_lower = m_dLimits.data();
+        m_cLimits.pos_upper = m_dLimits.data() + n;
+        m_cLimits.klim = m_dLimits.data() + 2 * n;
+        m_cLimits.vel_max = m_limits.size() == 4 * n ? m_dLimits.data() + 3 * n : nullptr;
+        m_cLimits.sampling_time = lt.samplingTime();
+    }
+    const blf_status called =
+        m_limitsTask >= 0 ? blf_fb_ik_solve_limits(h, &m_cModel, &m_cState, &m_cTasks,
+                                                   m_cHard.rows != 0 ? &m_cHard : nullptr, &m_cLimits, 1, d, status,
+                                                   nullptr, nullptr, nullptr)
+        : m_cHard.rows != 0
+            ? blf_fb_ik_solve_hard(h, &m_cModel, &m_cState, &m_cTasks, &m_cHard, 1, d, status, nullptr)
+            : blf_fb_ik_solve(h, &m_cModel, &m_cState, &m_cTasks, 1, d, status, nullptr);
     if (!blf::report(called, "QPInverseKinematics::advance")) return false;
     std::vector<double> nu(NV);
     if (!m_dData.download(nu.data(), NV) || !m_dInt.download(ints.data(), K + 1)) return false;
@@ -408,6 +462,9 @@ bool QPInverseKinematics::advance()
                   << (ints[K] == BLF_IK_BAD_INPUT ? "The robot state or a set point is not finite."
                       : ints[K] == BLF_IK_HARD_DEPENDENT
                           ? "The hard tasks are linearly dependent, conflicting or more than the unknowns."
+                      : ints[K] == BLF_IK_LIMITS_UNRESOLVED
+                          ? "The joint limits conflict with the hard tasks, or the active-set iteration did not "
+                            "resolve them."
                           : "The problem is not positive definite.")
                   << std::endl;
         return false;

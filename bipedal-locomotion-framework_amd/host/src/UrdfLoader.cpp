@@ -305,6 +305,9 @@ blf::RobotModel reorder(const blf::RobotModel& m, const std::vector<int>& perm,
         for (int a = 0; a < 9; ++a) out.jointRotation[9 * k + a] = m.jointRotation[9 * o + a];
         for (int a = 0; a < 3; ++a) out.jointAxis[3 * k + a] = m.jointAxis[3 * o + a];
         if (!m.jointType.empty()) out.jointType[k] = m.jointType[o];
+        if (!m.jointLower.empty()) out.jointLower[k] = m.jointLower[o];
+        if (!m.jointUpper.empty()) out.jointUpper[k] = m.jointUpper[o];
+        if (!m.jointVelocityLimit.empty()) out.jointVelocityLimit[k] = m.jointVelocityLimit[o];
         out.linkMass[k + 1] = m.linkMass[o + 1];
         for (int a = 0; a < 3; ++a) out.linkCom[3 * (k + 1) + a] = m.linkCom[3 * (o + 1) + a];
         for (int a = 0; a < 9; ++a) out.linkInertia[9 * (k + 1) + a] = m.linkInertia[9 * (o + 1) + a];
@@ -393,6 +396,9 @@ blf::RobotModel build(const XmlNode& robot, const blf::UrdfOptions& opt, std::ve
     m.jointAxis.assign(3 * n, 0.0);
     m.jointType.assign(n, BLF_JOINT_REVOLUTE);
     m.fixedJoint.assign(n, 0);
+    m.jointLower.assign(n, -HUGE_VAL);
+    m.jointUpper.assign(n, HUGE_VAL);
+    m.jointVelocityLimit.assign(n, HUGE_VAL);
     m.linkMass.assign(n + 1, 0.0);
     m.linkCom.assign(3 * (n + 1), 0.0);
     m.linkInertia.assign(9 * (n + 1), 0.0);
@@ -420,6 +426,21 @@ blf::RobotModel build(const XmlNode& robot, const blf::UrdfOptions& opt, std::ve
         if (!fixed && !(na > 0.0)) throw UrdfError{"joint " + names[k] + " has a zero axis"};
         for (int a = 0; a < 3; ++a) m.jointAxis[3 * k + a] = na > 0.0 ? ax[a] / na : xaxis[a];
         if (typ == "prismatic") m.jointType[k] = BLF_JOINT_PRISMATIC;
+        // <limit>: the range of a revolute / prismatic joint (a continuous joint has none), and the
+        // velocity limit of any moving joint; a missing attribute or a non-positive velocity: none
+        if (const XmlNode* lim = fixed ? nullptr : j->child("limit"))
+        {
+            const std::string *lo = lim->attr("lower"), *up = lim->attr("upper"), *vel = lim->attr("velocity");
+            if (typ != "continuous")
+            {
+                if (lo) m.jointLower[k] = number(*lo, "limit lower");
+                if (up) m.jointUpper[k] = number(*up, "limit upper");
+                if (m.jointLower[k] > m.jointUpper[k])
+                    throw UrdfError{"joint " + names[k] + " has a lower limit above its upper limit"};
+            }
+            const double v = vel ? number(*vel, "limit velocity") : 0.0;
+            if (v > 0.0) m.jointVelocityLimit[k] = v;
+        }
         const bool locked = opt.hasConsideredJoints
                             && std::find(opt.consideredJoints.begin(), opt.consideredJoints.end(), names[k])
                                    == opt.consideredJoints.end();

@@ -13,7 +13,12 @@ warm-up, median of `rounds` rounds, the variants alternating within a round.  On
     substitutions, two robots per wavefront);
   * with --hard, in the same rounds: blf_fb_ik_solve_hard and blf_fb_ik_integrate_hard (steps = 20)
     with robot.standing_ik_hard (both soles and the CoM's x, y: 14 hard rows), and their ratio to the
-    soft figures of the same run.
+    soft figures of the same run;
+  * with --limits (implies --hard), in the same rounds: blf_fb_ik_solve_limits and
+    blf_fb_ik_integrate_limits (steps = 20) with robot.humanoid24_joint_limits (sampling_time = dT) on
+    the same task set with the CoM target 2 cm above the nominal height, which straight legs cannot
+    reach, so both knees end on their lower bound; the hard calls on that raised task set, the ratio
+    limits / hard of the same run, the mean iters, and from these the time of one further iteration.
 
 Counted flops per robot-step, NV = n + 6, M = the task rows of non-zero weight: H and g from the task
 rows M (NV (NV + 1) + 2 NV), the Cholesky factorization NV^3 / 3, the two substitutions 2 NV^2.  The
@@ -21,7 +26,7 @@ kinematics and the task rows themselves are not counted.  Both calls stage the s
 to the host and wait for that copy before they launch (blf_c.h section 12), so every call here
 includes one stream synchronisation: the unfused sequence pays 20 of them, the fused call one.
 
-  timeout -k 10 600 python tools/ik_bench.py [--robots 16384] [--steps 20] [--rounds 5] [--hard]
+  timeout -k 10 600 python tools/ik_bench.py [--robots 16384] [--steps 20] [--rounds 5] [--hard] [--limits]
 (BLF_LIB=.../lib/libblf_<name>.so times a variant build, tools/build_variant.sh)
 """
 import argparse
@@ -76,7 +81,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--label", default="")
     ap.add_argument("--hard", action="store_true", help="also time the hard-task calls (section 12b)")
+    ap.add_argument("--limits", action="store_true", help="also time the joint-limit calls (section 12c)")
     args = ap.parse_args()
+    args.hard = args.hard or args.limits
     assert torch.cuda.is_available(), "needs a HIP device"
     h = native.Handle(0)
     prov = native.build_provenance()
@@ -134,6 +141,23 @@ def main():
 
         variants["solve_hard"] = lambda: h.fb_ik_solve(dm, start, tk, nu=nu, status=status, hard=hard)
         variants["fused_hard"] = fused_hard
+    if args.limits:
+        raised = dict(tasks, com_pos=tasks["com_pos"] + np.array([0.0, 0.0, 0.02]))
+        tkr = h.ik_tasks(B, n, **raised)
+        lim = h.ik_limits(**robot.humanoid24_joint_limits(model, sampling_time=DT))
+        iters = torch.zeros((B,), dtype=torch.int32, device="cuda")
+        active = torch.zeros((B, 2), dtype=torch.int64, device="cuda")
+
+        def fused_raised(limits=None):
+            restore()
+            h.fb_ik_integrate(dm, st, tkr, steps, DT, nu=nu, status=status, hard=hard, limits=limits, iters=iters,
+                              active=active)
+
+        variants["solve_hard_raised"] = lambda: h.fb_ik_solve(dm, start, tkr, nu=nu, status=status, hard=hard)
+        variants["solve_limits"] = lambda: h.fb_ik_solve(dm, start, tkr, nu=nu, status=status, hard=hard,
+                                                         limits=lim, iters=iters, active=active)
+        variants["fused_hard_raised"] = fused_raised
+        variants["fused_limits"] = lambda: fused_raised(lim)
     res = compare(variants, reps=args.reps, rounds=args.rounds)
     fused()
     f_state = {k: v.clone() for k, v in st.items()}
@@ -163,6 +187,25 @@ def main():
                           "fused_hard_ms": res["fused_hard"], "solve_hard_over_soft": res["solve_hard"][0] / res["solve"][0],
                           "fused_hard_over_soft_net": h_ms / f_ms, "fused_hard_ms_per_step_net": h_ms / steps,
                           "all_status_ok": ok_h, "label": args.label}), flush=True)
+    if args.limits:
+        variants["solve_limits"]()
+        ok_s, it_s = bool((status == 0).all()), float(iters.double().mean())
+        held = float(((active[:, 0] != 0) | (active[:, 1] != 0)).double().mean())
+        variants["fused_limits"]()
+        ok_l, it_l = bool((status == 0).all()), float(iters.double().mean()) / steps
+        hr_ms = res["fused_hard_raised"][0] - res["restore"][0]
+        l_ms = res["fused_limits"][0] - res["restore"][0]
+        ds = res["solve_limits"][0] - res["solve_hard_raised"][0]
+        print(json.dumps({"bench": "fb_ik_limits", "robots": B, "steps": steps,
+                          "solve_hard_raised_ms": res["solve_hard_raised"], "solve_limits_ms": res["solve_limits"],
+                          "fused_hard_raised_ms": res["fused_hard_raised"], "fused_limits_ms": res["fused_limits"],
+                          "solve_limits_over_hard": res["solve_limits"][0] / res["solve_hard_raised"][0],
+                          "fused_limits_over_hard_net": l_ms / hr_ms, "mean_iters_solve": it_s,
+                          "mean_iters_per_fused_step": it_l, "robots_with_a_bound_active": held,
+                          "ms_per_further_iteration_solve": ds / (it_s - 1.0) if it_s > 1.0 else None,
+                          "ms_per_further_iteration_fused_step": ((l_ms - hr_ms) / steps / (it_l - 1.0)
+                                                                  if it_l > 1.0 else None),
+                          "all_status_ok": ok_s and ok_l, "label": args.label}), flush=True)
     h.close()
 
 
