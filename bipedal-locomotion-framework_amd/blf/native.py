@@ -32,7 +32,7 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance",
             "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate",
             "blf_fb_ik_solve_hard", "blf_fb_ik_integrate_hard", "blf_fb_ik_solve_limits",
-            "blf_fb_ik_integrate_limits"]
+            "blf_fb_ik_integrate_limits", "blf_fb_ik_track"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -99,6 +99,13 @@ class IkLimits(ctypes.Structure):
     """blf_ik_limits (include/blf/blf_c.h section 12c); every pointer is device memory."""
     _fields_ = [("pos_lower", _vp), ("pos_upper", _vp), ("klim", _vp), ("vel_max", _vp),
                 ("sampling_time", _f64), ("max_iter", _i32), ("reserved", _i32)]
+
+
+class IkSchedule(ctypes.Structure):
+    """blf_ik_schedule (include/blf/blf_c.h section 12d); every pointer is device memory."""
+    _fields_ = [("steps", _i32), ("reserved", _i32), ("stance_rows", ctypes.c_uint32),
+                ("reserved2", ctypes.c_uint32), ("contact", _vp), ("se3_pose", _vp), ("se3_twist", _vp),
+                ("com_pos", _vp), ("com_vel", _vp)]
 
 
 IK_OK, IK_NOT_POSITIVE, IK_BAD_INPUT = 0, 1, 2   # per-robot status of fb_ik_solve / fb_ik_integrate
@@ -255,6 +262,10 @@ def lib():
                                                  ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard),
                                                  ctypes.POINTER(IkLimits), _i64, _i32, _f64, _vp, _vp, _vp, _vp,
                                                  _vp]
+        L.blf_fb_ik_track.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
+                                      ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard), ctypes.POINTER(IkLimits),
+                                      ctypes.POINTER(IkSchedule), _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp]
         L.blf_dcm_mpc_flops_per_iter.restype = _f64
         L.blf_set_qp_launch_mode.argtypes = [_i32, _i32]
         for name in EXPORTED:
@@ -1179,6 +1190,71 @@ class Handle:
                                                   ctypes.byref(tasks.c), ctypes.byref(hard), B, int(steps),
                                                   float(dT), np_, sp, _stream(stream)))
         return state, (nu if nu is not False else None), (status if status is not False else None)
+
+    # ---- reference tracking (include/blf/blf_c.h section 12d) ------------------------------------
+    def ik_schedule(self, batch, nse3, steps, stance_rows=0, contact=None, se3_pose=None, se3_twist=None,
+                    com_pos=None, com_vel=None):
+        """Build a blf_ik_schedule for `batch` robots, K = nse3 SE3 tasks and T = steps steps:
+        stance_rows an int in ik_hard()'s bit layout (SE3 bits only, e.g. ik_hard(se3=...).rows), contact
+        [B,K,T] int32 or None (never in contact), se3_pose [B,K,T,12], se3_twist [B,K,T,6] or None,
+        com_pos / com_vel [B,T,3].  swing_foot_eval's outputs for B*K lists and T query times fit as they
+        stand ([B*K,T,...] device tensors are passed on without a copy); host arrays are uploaded.
+        Returns an object with the struct (.c) and the tensors (.t) it keeps alive."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+
+        class _T:
+            pass
+        sc = _T()
+        B, K, T = int(batch), int(nse3), int(steps)
+        c = IkSchedule()
+        c.steps, c.reserved, c.stance_rows, c.reserved2 = T, 0, int(stance_rows), 0
+        spec = dict(contact=(contact, torch.int32, B * K * T), se3_pose=(se3_pose, torch.float64, B * K * T * 12),
+                    se3_twist=(se3_twist, torch.float64, B * K * T * 6), com_pos=(com_pos, torch.float64, B * T * 3),
+                    com_vel=(com_vel, torch.float64, B * T * 3))
+        sc.t = {}
+        for k, (a, dt, count) in spec.items():
+            if a is None or (K == 0 and k in ("contact", "se3_pose", "se3_twist")):
+                continue
+            t = a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=dt).contiguous().to(dev)
+            if t.numel() != count:
+                raise ValueError(f"ik_schedule: {k} has {t.numel()} elements, expected {count}")
+            sc.t[k] = t
+            setattr(c, k, _ptr(t, dt, tuple(t.shape), k))
+        sc.c, sc.batch, sc.nse3, sc.steps = c, B, K, T
+        return sc
+
+    def fb_ik_track(self, dm, state, tasks, schedule, dT, hard=None, limits=None, joint_traj=None, base_traj=None,
+                    nu_traj=None, status=None, fail_step=None, iters=None, active=None, stream=None):
+        """blf_fb_ik_track: schedule.steps x (section 12c's solve with step t's set points and each
+        robot's own hard rows of step t, one Euler step of dT) in one launch, in place on `state`.
+        hard (an ik_hard()): rows hard at every step; limits (an ik_limits()) or None: no box.  Every
+        output is optional (None: allocated, False: not requested).  Returns a dict: state, joint_traj
+        [T,B,n], base_traj [T,B,12], nu_traj [T,B,6+n], status, fail_step, iters [B] int32, active
+        [B,2] int64 (None for what was not requested)."""
+        torch = _torch()
+        B, n = state["joint_pos"].shape
+        dev = state["joint_pos"].device
+        T = schedule.steps
+        shapes = dict(joint_traj=((T, B, n), torch.float64), base_traj=((T, B, 12), torch.float64),
+                      nu_traj=((T, B, 6 + n), torch.float64), status=((B,), torch.int32),
+                      fail_step=((B,), torch.int32), iters=((B,), torch.int32), active=((B, 2), torch.int64))
+        given = dict(joint_traj=joint_traj, base_traj=base_traj, nu_traj=nu_traj, status=status,
+                     fail_step=fail_step, iters=iters, active=active)
+        out, ptr = {}, {}
+        for k, (shape, dt) in shapes.items():
+            a = given[k]
+            if a is None:
+                a = torch.zeros(shape, dtype=dt, device=dev)
+            out[k] = a if a is not False else None
+            ptr[k] = _ptr(a, dt, shape, k) if a is not False else None
+        _check(lib().blf_fb_ik_track(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
+                                     ctypes.byref(tasks.c), ctypes.byref(hard) if hard is not None else None,
+                                     ctypes.byref(limits.c) if limits is not None else None,
+                                     ctypes.byref(schedule.c), B, float(dT), ptr["joint_traj"], ptr["base_traj"],
+                                     ptr["nu_traj"], ptr["status"], ptr["fail_step"], ptr["iters"], ptr["active"],
+                                     _stream(stream)))
+        return dict(out, state=state)
 
     # ---- config 5: the closed loop's maps (DESIGN.md section 11) ----------------------------------
     def fb_dcm(self, dm, state, omega=None, column=0, com=None, xi=None, stream=None):

@@ -296,6 +296,49 @@ def standing_ik_hard(model):
     return dict(se3=[[True] * 6 for _ in range(F)], com=[True, True, False])
 
 
+def walking_ik_schedule(model, states, steps, dT, shift=None, step_length=0.04, step_height=0.02,
+                        liftoff=(0.1, 0.6), swing=0.3, lean=0.5):
+    """A short walk for blf_fb_ik_track (include/blf/blf_c.h section 12d) on humanoid24, as host arrays:
+    one cycle of `steps` steps of dT in which each sole takes one step of `step_length` forward
+    (apex `step_height`).  Sole k lifts off at (liftoff[k] + shift[b]) mod 1 of robot b's cycle and
+    lands `swing` of a cycle later (after the call's last step if that is past the cycle's end), so
+    robots with different shift[b] are in different phases; shift None: robot b at b / 2 mod 1, the
+    neighbours half a cycle apart.  Before its step a sole stands on its sole_null_poses pose.
+    The CoM reference leans towards the stance sole while the other one swings: `lean` of the way from
+    the middle of the soles to the stance sole at mid-swing (sin^2 over the swing), at the nominal height.
+    Returns dict(contact_pose [B*K,2,12], contact_time [B*K,2,2], ncontacts [B*K], tq [B*K,steps]: the
+    arguments of native.Handle.swing_foot_eval, list b*K + k being sole k of robot b; step_height;
+    com_pos [B,steps,3]; stance_rows: every row of both sole tasks; steps)."""
+    B = states["joint_pos"].shape[0]
+    K = len(model["frame_link"])
+    if K != 2:
+        raise ValueError("walking_ik_schedule: the model must have two sole frames")
+    shift = np.arange(B) * 0.5 % 1.0 if shift is None else np.asarray(shift, dtype=np.float64) % 1.0
+    if shift.shape != (B,):
+        raise ValueError("walking_ik_schedule: shift must be [B]")
+    P = steps * dT
+    null = sole_null_poses(model, states)
+    cp = np.repeat(null[:, :, None, :], 2, axis=2)          # [B, K, 2, 12]
+    cp[:, :, 1, 0] += step_length
+    off = (np.asarray(liftoff, dtype=np.float64)[None, :] + shift[:, None]) % 1.0   # [B, K]
+    ct = np.empty((B, K, 2, 2))
+    ct[:, :, 0, 0], ct[:, :, 0, 1] = -P, off * P
+    ct[:, :, 1, 0], ct[:, :, 1, 1] = (off + swing) * P, 3.0 * P
+    t = np.arange(steps) * dT
+    tq = np.broadcast_to(t, (B * K, steps)).copy()
+    # the CoM reference: s_k(t) = sin^2 over sole k's swing, 0 outside
+    u = (t[None, None, :] - ct[:, :, 0, 1, None]) / (swing * P)
+    s = np.where((u > 0.0) & (u < 1.0), np.sin(np.pi * np.clip(u, 0.0, 1.0)) ** 2, 0.0)   # [B, K, steps]
+    mid = null[:, :, :2].mean(axis=1)                        # [B, 2]
+    com = np.empty((B, steps, 3))
+    com[:, :, :2] = mid[:, None, :] + lean * (s[:, 0, :, None] * (null[:, None, 1, :2] - mid[:, None, :])
+                                              + s[:, 1, :, None] * (null[:, None, 0, :2] - mid[:, None, :]))
+    com[:, :, 2] = nominal_com_offset(model)[2] - sole_offsets(model)[:, 2].mean()
+    return dict(contact_pose=cp.reshape(B * K, 2, 12), contact_time=ct.reshape(B * K, 2, 2),
+                ncontacts=np.full(B * K, 2, dtype=np.int32), tq=tq, step_height=float(step_height),
+                com_pos=com, stance_rows=(1 << (6 * K)) - 1, steps=int(steps))
+
+
 # joint name's last word(s) -> (lower, upper) rad, velocity limit rad/s.  Positive knee angles fold the
 # leg (the shank swings back), so the knee's range starts at straight.
 _JOINT_RANGE = {"hip_yaw": (-0.8, 0.8, 6.0), "hip_roll": (-0.5, 0.5, 6.0), "hip_pitch": (-1.9, 0.8, 6.0),

@@ -827,9 +827,10 @@ blf_status blf_fbd_euler_integrate(blf_handle* handle, const blf_fb_model* model
 // device memory: they are copied to the host on the call's stream and checked there before the
 // launch (section 12: a staged copy).
 // wout (or null): receives the staged se3_weight 6K | se3_kp 2K | com_weight 3 when batch > 0.
+// setpoints = false (section 12d): tasks->se3_pose and com_pos are not read, so not required.
 static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_model* model,
                            const blf_fb_state* state, const blf_ik_tasks* t, int64_t batch,
-                           hipStream_t s, double* wout = nullptr)
+                           hipStream_t s, double* wout = nullptr, bool setpoints = true)
 {
     BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
     BLF_REQUIRE(model != nullptr && state != nullptr, "%s: null model / state", fn);
@@ -856,8 +857,8 @@ static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_mode
                 "%s: com_kp=%g, must be finite and >= 0", fn, t->com_kp);
     if (batch == 0) return BLF_OK;
     BLF_REQUIRE(state->base_pos && state->base_rot && state->joint_pos, "%s: null state buffer", fn);
-    BLF_REQUIRE(K == 0 || t->se3_pose, "%s: null se3_pose", fn);
-    BLF_REQUIRE(t->com_weight == nullptr || t->com_pos, "%s: com_weight given without com_pos", fn);
+    BLF_REQUIRE(!setpoints || K == 0 || t->se3_pose, "%s: null se3_pose", fn);
+    BLF_REQUIRE(!setpoints || t->com_weight == nullptr || t->com_pos, "%s: com_weight given without com_pos", fn);
     BLF_REQUIRE(t->joint_pos != nullptr, "%s: null joint_pos set point", fn);
     // the staged copy: se3_weight 6K | se3_kp 2K | com_weight 3 | joint_weight n | joint_kp n
     double hbuf[8 * BLF_IK_MAX_SE3_TASKS + 3 + 2 * BLF_FBD_MAX_DOFS];
@@ -900,10 +901,12 @@ static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_mode
 // soft path) and the pivot bound in *tau.
 static blf_status check_ik_hard(const char* fn, blf_handle* handle, const blf_fb_model* model,
                                 const blf_fb_state* state, const blf_ik_tasks* t, const blf_ik_hard* hard,
-                                int64_t batch, hipStream_t s, uint32_t* slots, double* tau)
+                                int64_t batch, hipStream_t s, uint32_t* slots, double* tau,
+                                double* wout = nullptr, bool setpoints = true)
 {
-    double w[8 * BLF_IK_MAX_SE3_TASKS + 3];
-    const blf_status st = check_ik(fn, handle, model, state, t, batch, s, w);
+    double wown[8 * BLF_IK_MAX_SE3_TASKS + 3];
+    double* w = wout ? wout : wown;
+    const blf_status st = check_ik(fn, handle, model, state, t, batch, s, w, setpoints);
     if (st != BLF_OK) return st;
     *slots = 0;
     *tau = 0.0;
@@ -1010,6 +1013,55 @@ blf_status blf_fb_ik_integrate_limits(blf_handle* handle, const blf_fb_model* mo
     BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_fb_ik_integrate_limits: dT=%g, must be finite and positive", dT);
     return ik_limits_call("blf_fb_ik_integrate_limits", handle, model, state, tasks, hard, limits, batch, steps, dT,
                           nu, status, iters, active, (hipStream_t)stream);
+}
+
+blf_status blf_fb_ik_track(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
+                           const blf_ik_tasks* tasks, const blf_ik_hard* hard, const blf_ik_limits* limits,
+                           const blf_ik_schedule* schedule, int64_t batch, double dT, double* joint_traj,
+                           double* base_traj, double* nu_traj, int32_t* status, int32_t* fail_step, int32_t* iters,
+                           uint64_t* active, void* stream)
+{
+    const char* fn = "blf_fb_ik_track";
+    hipStream_t s = (hipStream_t)stream;
+    BLF_REQUIRE(schedule != nullptr, "%s: null schedule", fn);
+    BLF_REQUIRE(schedule->steps >= 1, "%s: steps=%d, must be >= 1", fn, schedule->steps);
+    BLF_REQUIRE(schedule->reserved == 0 && schedule->reserved2 == 0u, "%s: schedule->reserved must be 0", fn);
+    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "%s: dT=%g, must be finite and positive", fn, dT);
+    uint32_t slots = 0;
+    double tau = 0.0, w[8 * BLF_IK_MAX_SE3_TASKS + 3];
+    const blf_status st = check_ik_hard(fn, handle, model, state, tasks, hard, batch, s, &slots, &tau, w, false);
+    if (st != BLF_OK) return st;
+    const int K = tasks->nse3;
+    const uint32_t stance = schedule->stance_rows;
+    BLF_REQUIRE((uint64_t)stance >> (6 * K) == 0u, "%s: stance_rows=0x%x has bits outside the %d SE3 tasks", fn,
+                stance, K);
+    if (batch > 0)
+        for (int r = 0; r < 6 * K; ++r)
+            BLF_REQUIRE(!((stance >> r) & 1u) || w[r] > 0.0, "%s: stance row %d of SE3 task %d has weight 0", fn,
+                        r % 6, r / 6);
+    blf_ik_limits lim;
+    if (limits != nullptr) {
+        lim = *limits;
+        BLF_REQUIRE(limits->reserved == 0, "%s: limits->reserved must be 0", fn);
+        BLF_REQUIRE(std::isfinite(limits->sampling_time) && limits->sampling_time > 0.0,
+                    "%s: sampling_time=%g, must be finite and positive", fn, limits->sampling_time);
+        BLF_REQUIRE(limits->max_iter >= 0, "%s: max_iter=%d, must be >= 0", fn, limits->max_iter);
+    }
+    if (batch == 0) return BLF_OK;
+    BLF_REQUIRE(state->base_vel && state->joint_vel, "%s: null state buffer", fn);
+    BLF_REQUIRE(K == 0 || schedule->se3_pose, "%s: null schedule->se3_pose", fn);
+    BLF_REQUIRE(tasks->com_weight == nullptr || schedule->com_pos, "%s: com_weight given without schedule->com_pos",
+                fn);
+    if (limits != nullptr) {
+        const blf_status sl = check_ik_limits(fn, limits, model->ndof, s, &lim.max_iter);
+        if (sl != BLF_OK) return sl;
+    }
+    if (fb_ik_track_lds_bytes(model->ndof, K) > 160 * 1024)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    // tau of a call without `hard`: the default (stance rows may still be hard)
+    return launch_fb_ik_track(model, state, tasks, limits ? &lim : nullptr, schedule, batch, dT, joint_traj,
+                              base_traj, nu_traj, status, fail_step, iters, active, s, slots, stance,
+                              tau > 0.0 ? tau : 1.0e-8);
 }
 
 blf_status blf_fb_ik_solve(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,

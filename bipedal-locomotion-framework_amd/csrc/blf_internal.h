@@ -155,7 +155,15 @@ blf_status launch_fb_ik_limits(const blf_fb_model* md, const blf_fb_state* st, c
                                const blf_ik_limits* lim, int64_t batch, int32_t steps, double dT, double* nu,
                                int32_t* status, int32_t* iters, uint64_t* active, hipStream_t s, uint32_t slots,
                                double tau);
+// Section 12d: sch's arrays already validated; base / stance: hard->rows and schedule->stance_rows as
+// bits of the task-row table (see launch_fb_ik); lim == nullptr: no box (max_iter is then unused).
+blf_status launch_fb_ik_track(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t,
+                              const blf_ik_limits* lim, const blf_ik_schedule* sch, int64_t batch, double dT,
+                              double* joint_traj, double* base_traj, double* nu_traj, int32_t* status,
+                              int32_t* fail_step, int32_t* iters, uint64_t* active, hipStream_t s, uint32_t base,
+                              uint32_t stance, double tau);
 size_t fb_ik_lds_bytes(int n, int K, bool limits = false);
+size_t fb_ik_track_lds_bytes(int n, int K);
 blf_status launch_posture_reference(const blf_posture_law* law, const double* com, const double* vrp,
                                     int64_t vstride, int64_t batch, double* qref, hipStream_t s);
 blf_status launch_fbk_euler(int n, double rho, double* pos, double* rot, double* joints,

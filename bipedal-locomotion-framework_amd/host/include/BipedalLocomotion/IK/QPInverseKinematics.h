@@ -85,6 +85,18 @@ public:
 
     std::vector<std::string> getTaskNames() const;
 
+    /**
+     * Switch a task between weighted (1) and hard (0), also after finalize() and between advance()
+     * calls (the task set itself stays fixed): the adapter's form of a contact flag (a stance foot's task is hard, a swing foot's weighted; the
+     * batched form is blf_fb_ik_track's schedule, section 12d).  For an SE3Task or a CoMTask that was
+     * added at priority 1 with every weight > 0: while hard its rows hold exactly and enter H with
+     * the weights it was added with.  hardRows() reflects the switch.  False with a
+     * "[QPInverseKinematics::setTaskPriority] ..." line for an unknown name, a
+     * priority above 1, a task of another kind, one that was added at priority 0, or one with a zero
+     * weight; the task then keeps its priority.
+     */
+    bool setTaskPriority(const std::string& taskName, unsigned int priority);
+
     /** Resolve the frames and fix the task set; false without a model or with an unknown frame, or
      * when the JointLimitsTask's sizes do not match the model or it asks for the model's limits
      * ("use_model_limits") and the model has none. */
@@ -108,7 +120,7 @@ public:
     /** The limits of the last advance(); every pointer is null without a JointLimitsTask. */
     const blf_ik_limits& deviceLimits() const { return m_cLimits; }
 
-    /** Section 12b's mask of the hard tasks added so far: bits 6k..6k+5 for the k-th SE3 task (in
+    /** Section 12b's mask of the tasks that are hard now: bits 6k..6k+5 for the k-th SE3 task (in
      * the order they were added) when it is hard, bits 24..26 for a hard CoM task. */
     uint32_t hardRows() const;
 
@@ -119,6 +131,7 @@ private:
         std::shared_ptr<IKLinearTask> task;
         std::vector<double> weight;
         bool hard;
+        bool weighted{false};   // added at priority 1 (what setTaskPriority() may switch)
     };
     std::vector<Entry> m_tasks;
     std::vector<int32_t> m_frames;

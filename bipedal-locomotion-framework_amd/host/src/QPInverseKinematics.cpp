@@ -222,7 +222,46 @@ bool QPInverseKinematics::addTask(std::shared_ptr<IKLinearTask> task, const std:
     if (kind == IKLinearTask::Kind::CoM) m_comTask = static_cast<int>(m_tasks.size());
     if (joint) m_jointTask = static_cast<int>(m_tasks.size());
     m_tasks.push_back(Entry{taskName, std::move(task), std::vector<double>(weight.data(), weight.data() + rows),
-                            false});
+                            false, true});
+    return true;
+}
+
+bool QPInverseKinematics::setTaskPriority(const std::string& taskName, unsigned int priority)
+{
+    constexpr const char* where = "[QPInverseKinematics::setTaskPriority] ";
+    if (priority > 1)
+    {
+        std::cerr << where << "The task " << taskName << " cannot get priority " << priority
+                  << ": only hard (priority 0) and weighted (priority 1) tasks are supported." << std::endl;
+        return false;
+    }
+    const auto it = std::find_if(m_tasks.begin(), m_tasks.end(), [&](const Entry& e) { return e.name == taskName; });
+    if (it == m_tasks.end())
+    {
+        std::cerr << where << "The task named " << taskName << " does not exist." << std::endl;
+        return false;
+    }
+    const IKLinearTask::Kind kind = it->task->kind();
+    if (kind != IKLinearTask::Kind::SE3 && kind != IKLinearTask::Kind::CoM)
+    {
+        std::cerr << where << "The task " << taskName << " is not an SE3 or a CoM task: its priority is fixed."
+                  << std::endl;
+        return false;
+    }
+    if (!it->weighted)
+    {
+        std::cerr << where << "The task " << taskName << " was added at priority 0: it has no weights of its own "
+                     "to return to, so its priority is fixed."
+                  << std::endl;
+        return false;
+    }
+    if (std::any_of(it->weight.begin(), it->weight.end(), [](double w) { return !(w > 0.0); }))
+    {
+        std::cerr << where << "The task " << taskName << " has a zero weight: a hard row needs a positive one."
+                  << std::endl;
+        return false;
+    }
+    it->hard = priority == 0;
     return true;
 }
 

@@ -98,7 +98,7 @@ const char* blf_last_error(void);
  * is additive: it adds blf_rls_advance and blf_contact_rls_advance and changes no existing entry
  * point or struct.  blf_swing_foot_eval and blf_so3_eval, and later blf_fb_ik_solve_hard and
  * blf_fb_ik_integrate_hard (section 12b), then blf_fb_ik_solve_limits and
- * blf_fb_ik_integrate_limits (section 12c), were added within ABI 3 (no existing
+ * blf_fb_ik_integrate_limits (section 12c), then blf_fb_ik_track (section 12d), were added within ABI 3 (no existing
  * entry point or struct changed, so the number stays): a caller detects them by symbol
  * (dlsym).  ABI 2 (0.2.0) added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
  * a caller built against an older header must zero-initialise these structs (`= {0}`), since the
@@ -900,6 +900,70 @@ blf_status blf_fb_ik_integrate_limits(blf_handle* handle, const blf_fb_model* mo
                                       double dT, double* nu /* [B][6+n], the last step's, or NULL */,
                                       int32_t* status /* [B] or NULL */, int32_t* iters /* [B] or NULL */,
                                       uint64_t* active /* [B][2] or NULL */, void* stream);
+
+/* ---- 12d. Reference tracking: per-step set points and a per-robot, per-step contact schedule ----
+ * blf_fb_ik_track is blf_fb_ik_integrate_limits with the set points and the hard mask indexed by the
+ * step: T steps in one launch, robot b following its own references with its own feet planted.  The
+ * schedule's arrays are blf_swing_foot_eval's outputs for L = B*K lists (list b*K + k is SE3 task k of
+ * robot b) and Q = T query times, as they stand.
+ *   Per-step solve.  Step t = 0 .. T-1 of robot b runs section 12c's solve at the robot's current state
+ *     with the set points of index t, then takes blf_fbk_euler_integrate's single step of dT.
+ *   Set points.  tasks->se3_pose, se3_twist, com_pos and com_vel are not read and may be NULL; the
+ *     joint task's joint_pos / joint_vel stay [B][n] and are held over the call.  Every shared array
+ *     (weights, gains, frames, limits) is used as in section 12.
+ *   Hard rows.  rows(b,t) = hard->rows | union over k of (contact[b][k][t] != 0 ? stance_rows &
+ *     (0x3F << 6k) : 0).  "At most 6 + n hard rows" applies to each robot's own rows(b,t); a
+ *     violation, like any failed pivot of S with W empty, is BLF_IK_HARD_DEPENDENT for that robot only.
+ *     A hard row's weight only conditions H (section 12b).  tau is hard->rel_pivot_min, or the default
+ *     when hard is NULL.
+ *   Trajectories (each may be NULL) are step-major: slice t holds the state, or nu, after step t for the
+ *     whole batch, so slice t of joint_traj is directly a blf_joint_impedance q_ref.
+ *   Final state.  `state` ends at the state after the last completed step; base_vel and joint_vel
+ *     receive the last nu (NaN for a failed robot, as in section 12).
+ *   Failed robots.  A robot whose step fails keeps the state before that step (section 12); its status
+ *     is the first non-zero one, fail_step [B] (or NULL) that step and -1 for a robot that did not
+ *     fail; its trajectory entries from that step on are NaN; it reads no later set point.  A
+ *     non-finite set point of step t makes the robot BLF_IK_BAD_INPUT at step t, not before (a
+ *     non-finite joint set point or a bad frame index: at step 0).
+ *   iters is summed over the steps the robot ran, active is the last step's (section 12c).
+ *   limits == NULL: no box; every step is then section 12b's solve (to rounding, not bit for bit: the
+ *     call still runs section 12c's iteration, which ends after its first solve; iters counts it).
+ * Three equalities:
+ *   P1  a T-step call equals, bit for bit, T one-step calls with the schedule's slices (for robots that
+ *       do not fail: a one-step call starts every robot afresh);
+ *   P2  when every robot has the same rows(.,t) at every step and limits != NULL, the call equals, bit
+ *       for bit, T x blf_fb_ik_integrate_limits(steps = 1) with that mask and step t's set points;
+ *   P3  a robot's result does not depend on which robot shares its wavefront: a row its neighbour
+ *       holds hard and it does not enters its solve as a null row (zero in Y, e_i in S, zero right-hand
+ *       side), which contributes exact zeros, so the equality is bit for bit.
+ * Call-level errors: section 12c's, and BLF_ERR_INVALID_ARGUMENT for a null schedule, steps < 1, a
+ * reserved field != 0, a stance_rows bit outside the SE3 tasks present, a row of hard->rows |
+ * stance_rows whose weight is 0 (checked with the staged weights, so only when batch > 0), or a
+ * missing required pointer (se3_pose when nse3 > 0, com_pos iff com_weight, state->base_vel /
+ * joint_vel).  batch == 0: BLF_OK.  A refused call leaves every output untouched. */
+typedef struct blf_ik_schedule {
+    int32_t  steps;          /* T >= 1 */
+    int32_t  reserved;       /* must be 0 */
+    uint32_t stance_rows;    /* section 12b's bit layout, SE3 bits only (bits 0..6*nse3-1): the rows of
+                                task k that are hard at a step where contact[b][k][t] != 0 */
+    uint32_t reserved2;      /* must be 0 */
+    const int32_t* contact;  /* [B][K][T] or NULL (never in contact): blf_swing_foot_eval's in_contact
+                                for L = B*K lists, Q = T, as it stands */
+    const double* se3_pose;  /* [B][K][T][12]: blf_swing_foot_eval's pose output as it stands */
+    const double* se3_twist; /* [B][K][T][6] or NULL (zero): its twist output as it stands */
+    const double* com_pos;   /* [B][T][3]; required iff tasks->com_weight */
+    const double* com_vel;   /* [B][T][3] or NULL */
+} blf_ik_schedule;
+
+blf_status blf_fb_ik_track(blf_handle* handle, const blf_fb_model* model,
+                           const blf_fb_state* state /* in place */, const blf_ik_tasks* tasks,
+                           const blf_ik_hard* hard /* or NULL */, const blf_ik_limits* limits /* or NULL: no box */,
+                           const blf_ik_schedule* schedule, int64_t batch, double dT,
+                           double* joint_traj /* [T][B][n] or NULL */,
+                           double* base_traj /* [T][B][12] (p, R) or NULL */,
+                           double* nu_traj /* [T][B][6+n] or NULL */, int32_t* status /* [B] or NULL */,
+                           int32_t* fail_step /* [B] or NULL */, int32_t* iters /* [B] or NULL */,
+                           uint64_t* active /* [B][2] or NULL */, void* stream);
 
 /* Algorithmic flop count of one IPM iteration of one problem (what the fp64 roofline field
  * of bench.py is computed from); `active_facets` = sum_k nfacets[k]. */

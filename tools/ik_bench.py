@@ -18,7 +18,17 @@ warm-up, median of `rounds` rounds, the variants alternating within a round.  On
     blf_fb_ik_integrate_limits (steps = 20) with robot.humanoid24_joint_limits (sampling_time = dT) on
     the same task set with the CoM target 2 cm above the nominal height, which straight legs cannot
     reach, so both knees end on their lower bound; the hard calls on that raised task set, the ratio
-    limits / hard of the same run, the mean iters, and from these the time of one further iteration.
+    limits / hard of the same run, the mean iters, and from these the time of one further iteration;
+  * with --track, instead of the above: B walking humanoids (robot.walking_ik_schedule, one cycle of
+    `steps` steps, half the robots half a cycle apart) through swing_foot_eval and blf_fb_ik_track
+    (section 12d; joint_traj and status requested), and in the same rounds: blf_fb_ik_track with every
+    robot in the same phase (one mask per step for the whole batch: what the per-robot masks add);
+    blf_fb_ik_integrate_limits over `steps` steps with a uniform mask (both soles and the CoM's x, y)
+    and held set points, the fused call a user had before; blf_fb_ik_track on exactly that problem (no
+    contact array, step 0's set points at every step: bit for bit the same arithmetic, section 12d's P2,
+    so the ratio is the track kernel's own overhead); and the unfused route to per-step set
+    points a user had before, `steps` x { blf_fb_ik_solve_limits with step t's set points and that
+    uniform mask; blf_fbk_euler_integrate }.
 
 Counted flops per robot-step, NV = n + 6, M = the task rows of non-zero weight: H and g from the task
 rows M (NV (NV + 1) + 2 NV), the Cholesky factorization NV^3 / 3, the two substitutions 2 NV^2.  The
@@ -27,6 +37,7 @@ to the host and wait for that copy before they launch (blf_c.h section 12), so e
 includes one stream synchronisation: the unfused sequence pays 20 of them, the fused call one.
 
   timeout -k 10 600 python tools/ik_bench.py [--robots 16384] [--steps 20] [--rounds 5] [--hard] [--limits]
+  timeout -k 10 600 python tools/ik_bench.py --track [--robots 16384] [--steps 20] [--rounds 5]
 (BLF_LIB=.../lib/libblf_<name>.so times a variant build, tools/build_variant.sh)
 """
 import argparse
@@ -73,6 +84,113 @@ def counted_flops(NV, M):
     return M * (NV * (NV + 1) + 2 * NV) + NV ** 3 / 3.0 + 2 * NV ** 2
 
 
+def track_bench(h, args):
+    """--track: blf_fb_ik_track on walking humanoids against the fused and unfused calls of section 12c."""
+    B, T = args.robots, args.steps
+    model = robot.humanoid24()
+    n, K = model["n"], 2
+    host = robot.standing_states(model, B, seed=1, spread=0.2)
+    tasks = robot.standing_ik_tasks(model, host)
+    dm = h.fb_model(model)
+    lim = h.ik_limits(**robot.humanoid24_joint_limits(model, sampling_time=DT))
+    comxy = h.ik_hard(com=(True, True, False))
+    feet = h.ik_hard(**robot.standing_ik_hard(model))
+    dev = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).cuda()
+    start = {k: dev(host[k]) for k in native.FB_STATE_KEYS}
+    st = {k: v.clone() for k, v in start.items()}
+
+    def restore():
+        for k in native.FB_STATE_KEYS:
+            st[k].copy_(start[k])
+
+    def schedule(shift):
+        w = robot.walking_ik_schedule(model, host, T, DT, shift=shift)
+        sw = h.swing_foot_eval(dev(w["contact_pose"]), dev(w["contact_time"]), dev(w["ncontacts"], torch.int32),
+                               dev(w["tq"]), step_height=w["step_height"], outputs=("pose", "twist", "in_contact"))
+        return sw, w, h.ik_schedule(B, K, T, stance_rows=w["stance_rows"], contact=sw["in_contact"],
+                                    se3_pose=sw["pose"], se3_twist=sw["twist"], com_pos=w["com_pos"])
+
+    sw, w, sc = schedule(np.arange(B) % 2 * 0.5)
+    _, _, sc_same = schedule(np.zeros(B))
+    hold = lambda a: a[:, :, :1].expand(-1, -1, T, -1).contiguous()
+    sc_held = h.ik_schedule(B, K, T, se3_pose=hold(sw["pose"].reshape(B, K, T, 12)),
+                            se3_twist=hold(sw["twist"].reshape(B, K, T, 6)),
+                            com_pos=dev(np.repeat(w["com_pos"][:, :1], T, axis=1)))
+    tk = h.ik_tasks(B, n, **dict(tasks, se3_pose=None, com_pos=None))
+    # the calls a user had before: set points of step t as [B, ...] arrays of their own
+    pose = sw["pose"].reshape(B, K, T, 12)
+    twist = sw["twist"].reshape(B, K, T, 6)
+    com = dev(w["com_pos"])
+    tks = [h.ik_tasks(B, n, **dict(tasks, se3_pose=pose[:, :, t].contiguous(), se3_twist=twist[:, :, t].contiguous(),
+                                   com_pos=com[:, t].contiguous())) for t in range(T)]
+    jt = torch.empty((T, B, n), dtype=torch.float64, device="cuda")
+    status = torch.empty((B,), dtype=torch.int32, device="cuda")
+    fail = torch.empty((B,), dtype=torch.int32, device="cuda")
+    iters = torch.zeros((B,), dtype=torch.int32, device="cuda")
+    active = torch.zeros((B, 2), dtype=torch.int64, device="cuda")
+    nu = torch.empty((B, n + 6), dtype=torch.float64, device="cuda")
+    bv = torch.empty((B, 6), dtype=torch.float64, device="cuda")
+    jv = torch.empty((B, n), dtype=torch.float64, device="cuda")
+
+    def track(s=sc, hard=comxy):
+        restore()
+        h.fb_ik_track(dm, st, tk, s, DT, hard=hard, limits=lim, joint_traj=jt, base_traj=False, nu_traj=False,
+                      status=status, fail_step=fail, iters=iters, active=active)
+
+    def fused_uniform():
+        restore()
+        h.fb_ik_integrate(dm, st, tks[0], T, DT, nu=nu, status=status, hard=feet, limits=lim, iters=iters,
+                          active=active)
+
+    def unfused_uniform():
+        restore()
+        for t in range(T):
+            h.fb_ik_solve(dm, st, tks[t], nu=nu, status=status, hard=feet, limits=lim, iters=iters, active=active)
+            bv.copy_(nu[:, :6])
+            jv.copy_(nu[:, 6:])
+            h.fbk_euler_integrate(dm.c.rho, st["base_pos"], st["base_rot"], st["joint_pos"], bv, jv, 0.0, DT, DT)
+            jt[t].copy_(st["joint_pos"])
+
+    res = compare({"restore": restore, "track": track, "track_same_phase": lambda: track(sc_same),
+                   "track_held_uniform": lambda: track(sc_held, feet),
+                   "fused_uniform": fused_uniform, "unfused_uniform": unfused_uniform},
+                  reps=args.reps, rounds=args.rounds)
+    track()
+    ok_t, it_t = bool((status == 0).all()), float(iters.double().mean()) / T
+    nfail = int((fail >= 0).sum())
+    track(sc_same)
+    it_s = float(iters.double().mean()) / T
+    track(sc_held, feet)
+    held_jp = st["joint_pos"].clone()
+    fused_uniform()
+    ok_f, it_f = bool((status == 0).all()), float(iters.double().mean()) / T
+    same = torch.equal(held_jp, st["joint_pos"])
+    restore()
+    it_u = 0.0
+    for t in range(T):
+        h.fb_ik_solve(dm, st, tks[t], nu=nu, status=status, hard=feet, limits=lim, iters=iters, active=active)
+        it_u += float(iters.double().mean()) / T
+        h.fbk_euler_integrate(dm.c.rho, st["base_pos"], st["base_rot"], st["joint_pos"], nu[:, :6].contiguous(),
+                              nu[:, 6:].contiguous(), 0.0, DT, DT)
+    r0 = res["restore"][0]
+    net = {k: res[k][0] - r0 for k in ("track", "track_same_phase", "track_held_uniform", "fused_uniform",
+                                       "unfused_uniform")}
+    print(json.dumps({"bench": "fb_ik_track", "robots": B, "steps": T, "track_ms": res["track"],
+                      "track_same_phase_ms": res["track_same_phase"],
+                      "track_held_uniform_ms": res["track_held_uniform"], "fused_uniform_ms": res["fused_uniform"],
+                      "track_held_over_fused_uniform_net": net["track_held_uniform"] / net["fused_uniform"],
+                      "track_held_equals_fused_uniform_bitwise": same,
+                      "mean_iters_per_step_same_phase": it_s, "mean_iters_per_step_unfused_uniform": it_u,
+                      "unfused_uniform_ms": res["unfused_uniform"], "restore_ms": res["restore"],
+                      "track_ms_per_step_net": net["track"] / T,
+                      "track_over_fused_uniform_net": net["track"] / net["fused_uniform"],
+                      "track_over_same_phase_net": net["track"] / net["track_same_phase"],
+                      "track_over_unfused_uniform_net": net["track"] / net["unfused_uniform"],
+                      "mean_iters_per_step_track": it_t, "mean_iters_per_step_fused_uniform": it_f,
+                      "all_status_ok_track": ok_t, "failed_robots_track": nfail, "all_status_ok_fused_uniform": ok_f,
+                      "label": args.label}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--robots", type=int, default=16384)
@@ -82,6 +200,7 @@ def main():
     ap.add_argument("--label", default="")
     ap.add_argument("--hard", action="store_true", help="also time the hard-task calls (section 12b)")
     ap.add_argument("--limits", action="store_true", help="also time the joint-limit calls (section 12c)")
+    ap.add_argument("--track", action="store_true", help="time blf_fb_ik_track (section 12d) instead")
     args = ap.parse_args()
     args.hard = args.hard or args.limits
     assert torch.cuda.is_available(), "needs a HIP device"
@@ -90,6 +209,10 @@ def main():
     print(json.dumps({"bench": "provenance", "lib_src_hash": prov["lib_src_hash"],
                       "lib": os.path.basename(prov["lib"]), "matches_tree": prov["matches"],
                       "device": torch.cuda.get_device_name(0), "label": args.label}), flush=True)
+    if args.track:
+        track_bench(h, args)
+        h.close()
+        return
     B, steps = args.robots, args.steps
     model = robot.humanoid24()
     n = model["n"]
