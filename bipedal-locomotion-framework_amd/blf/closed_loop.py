@@ -24,6 +24,23 @@ The control period is the plan's knot spacing dt (the window moves one knot per 
 impedance runs at the integration step dT (1 kHz): a 50 Hz zero-order hold of the joint
 torques does not stabilise the robot's fast modes.  Every piece runs on the device; the host only
 enqueues.
+
+ClosedLoop(reference="ik") (opt-in; the default "posture" is the period above, launch for launch)
+replaces step 3 by the whole-body IK and tracks its trajectory slice by slice:
+
+  3a. plan -> CoM schedule:  com_pos, com_vel [B][T][3] from the measured DCM, the plan's first VRP
+                     and the window's first omega, T = ik["steps"] Euler steps of dt / T of the LIP's
+                     stable half (blf_dcm_com_reference); its c_ref starts at the measured CoM at
+                     period 0 and carries over, so feedback enters through the DCM only;
+  3b. IK:            blf_fb_ik_track over that schedule on the loop's own kinematic state (a copy of
+                     the initial pose that only the IK advances), both soles held on their null poses
+                     and CoM x, y hard, joint limits as a box: joint_traj, nu_traj;
+  3c. (lean=True)    the ankle lean term of step 3 about q_nominal = 0 as a per-robot bias;
+  4.  robot:         blf_fbd_euler_integrate_impedance_traj: integration step i tracks slice
+                     min(i // ceil(steps / T), T - 1), tau = kp (q_ref + q_bias - q) - kd (qdot - qd_ref)
+                     with qd_ref the joint rates of nu_traj.
+blf_fb_ik_track checks its shared weights through a staged copy and waits for it, so in this mode
+period() synchronises with the stream once per period.
 """
 import math
 
@@ -81,12 +98,25 @@ class _nullcontext:
 class ClosedLoop:
     """A batch of robots, each closed around its own plan (problems.make_batch with the phase
     table), on one device.  `states` is a host dict (robot.standing_states), `plan` the host
-    problem dict with a horizon of at least horizon + the number of periods to run."""
+    problem dict with a horizon of at least horizon + the number of periods to run.
+
+    reference="posture" (the default): the period of the module docstring.  reference="ik": the IK
+    period, with ik=dict(tasks=, hard=, limits=, steps=4, lean=True): tasks / hard / limits default to
+    robot.standing_ik_tasks, robot.standing_ik_hard (both soles and CoM x, y hard, the soles' targets
+    their null poses) and robot.humanoid24_joint_limits (sampling time dt / steps); steps IK slices per
+    period; lean adds the posture law's ankle lean term as the impedance's bias.  After a period
+    ik_status, ik_fail_step, ik_iters [B] and ik_active [B,2] hold blf_fb_ik_track's outputs,
+    joint_traj / nu_traj its trajectory and c_ref the CoM reference's end point."""
 
     def __init__(self, h, model, plan, states, horizon=100, dT=0.001, law=None,
                  contact_params=CONTACT_PARAMS, tol_polish=1e-4, stream=None, max_iter=MAX_ITER,
-                 cold_after_handover=None):
+                 cold_after_handover=None, reference="posture", ik=None):
         import torch
+        if reference not in ("posture", "ik"):
+            raise ValueError(f"reference={reference!r}: 'posture' or 'ik'")
+        if ik is not None and reference != "ik":
+            raise ValueError("ik= goes with reference='ik'")
+        self.reference = reference
         self.h, self.N, self.dT, self.stream = h, horizon, dT, stream
         dev = torch.device("cuda", h.device)
         t = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
@@ -128,9 +158,72 @@ class ClosedLoop:
         self.cold_after_handover = cold_after_handover
         self.warm_status = torch.empty((self.B,), dtype=torch.int32, device=dev)
         self.dyn_events = None   # a list: period() appends (start, end) events of its dynamics launch
+        if reference == "ik":
+            self._init_ik(model, states, law, dict(ik or {}), t, dev)
+
+    def _init_ik(self, model, states, law, ik, t, dev):
+        """The buffers of the IK period (module docstring, "reference='ik'"); everything is allocated here."""
+        import torch
+        h, B, n = self.h, self.B, model["n"]
+        unknown = set(ik) - {"tasks", "hard", "limits", "steps", "lean"}
+        if unknown:
+            raise ValueError(f"ik: unknown entries {sorted(unknown)}")
+        T = self.ik_steps = int(ik.get("steps", 4))
+        if T < 1:
+            raise ValueError("ik: steps must be >= 1")
+        self.ik_dT = self.dt / T
+        tasks = ik.get("tasks") if ik.get("tasks") is not None else R.standing_ik_tasks(model, states)
+        hard = ik.get("hard") if ik.get("hard") is not None else R.standing_ik_hard(model)
+        limits = (ik.get("limits") if ik.get("limits") is not None
+                  else R.humanoid24_joint_limits(model, sampling_time=self.ik_dT))
+        K = len(tasks["frame"])
+        # the set points come from the schedule: the soles' null poses held, the CoM from the plan
+        self.ik_tasks = h.ik_tasks(B, n, **dict(tasks, se3_pose=None, se3_twist=None, com_pos=None, com_vel=None))
+        self.ik_hard = h.ik_hard(**hard)
+        self.ik_limits = h.ik_limits(**limits)
+        # the loop's own kinematic state: the initial pose, advanced by the IK alone
+        self.ik_state = {k: t(states[k]) for k in native.FB_STATE_KEYS}
+        f64 = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        self.com_pos, self.com_vel = f64(B, T, 3), f64(B, T, 3)
+        self.c_ref, self.xi_end = f64(B, 2), f64(B, 2)
+        self.z_ref = t(np.asarray(tasks["com_pos"], dtype=np.float64)[:, 2])
+        sole = np.repeat(np.asarray(tasks["se3_pose"], dtype=np.float64)[:, :, None, :], T, axis=2)
+        self.ik_schedule = h.ik_schedule(B, K, T, stance_rows=(1 << (6 * K)) - 1,
+                                         contact=np.ones((B, K, T), dtype=np.int32), se3_pose=sole,
+                                         com_pos=self.com_pos, com_vel=self.com_vel)
+        self.joint_traj, self.nu_traj = f64(T, B, n), f64(T, B, 6 + n)
+        i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
+        self.ik_status, self.ik_fail_step, self.ik_iters = i32(B), i32(B), i32(B)
+        self.ik_active = torch.zeros((B, 2), dtype=torch.int64, device=dev)
+        self.lean = bool(ik.get("lean", True))
+        self.q_bias = f64(B, n) if self.lean else None
+        if self.lean:   # the ankle lean term alone: the posture law about q_nominal = 0
+            self.lean_law = h.posture_law(np.zeros(n), law["lean"])
+        self.steps_per_slice = -(-len(self.steps) // T)
+        self.traj = h.joint_impedance_traj(self.imp, self.joint_traj, self.steps_per_slice, qd_ref=self.nu_traj,
+                                           qd_offset=6, q_bias=self.q_bias)
+
+    def _ik_reference(self, out, s):
+        """Steps 3 and 4 of the IK period: the plan's CoM schedule, then the IK over it."""
+        h = self.h
+        if s == 0:   # the CoM reference starts at the measured CoM
+            import torch
+            with torch.cuda.stream(self.stream) if self.stream is not None else _nullcontext():
+                self.c_ref.copy_(self.com[:, :2])
+        h.dcm_com_reference(self.xi, out["vrp"], self.omega, self.z_ref, self.c_ref, self.ik_steps, self.ik_dT,
+                            column=s, com_pos=self.com_pos, com_vel=self.com_vel, xi_end=self.xi_end,
+                            stream=self.stream)
+        h.fb_ik_track(self.dm, self.ik_state, self.ik_tasks, self.ik_schedule, self.ik_dT, hard=self.ik_hard,
+                      limits=self.ik_limits, joint_traj=self.joint_traj, base_traj=False, nu_traj=self.nu_traj,
+                      status=self.ik_status, fail_step=self.ik_fail_step, iters=self.ik_iters,
+                      active=self.ik_active, stream=self.stream)
+        if self.lean:
+            h.posture_reference(self.lean_law, self.com, out["vrp"], q_ref=self.q_bias, stream=self.stream)
 
     def period(self):
-        """One control period (stream-ordered; nothing synchronises).  Returns the plan."""
+        """One control period (stream-ordered).  Returns the plan.  With reference="posture" nothing
+        synchronises; with reference="ik" blf_fb_ik_track checks its shared weights through a staged
+        copy and waits for it, so the host synchronises with the stream once per period."""
         h, s, N = self.h, self.s, self.N
         if s + N > self.omega.shape[1]:
             raise ValueError(f"the plan ends at knot {self.omega.shape[1]}; period {s} needs {s + N}")
@@ -157,7 +250,10 @@ class ClosedLoop:
             out = h.dcm_mpc_solve(w, self.params, out=self.bufs[s % 2], warm=warm,
                                   lambda_out=True, stream=self.stream)
         self.bufs[s % 2] = out
-        h.posture_reference(self.law, self.com, out["vrp"], q_ref=self.q_ref, stream=self.stream)
+        if self.reference == "ik":
+            self._ik_reference(out, s)
+        else:
+            h.posture_reference(self.law, self.com, out["vrp"], q_ref=self.q_ref, stream=self.stream)
         # integrate(0, T) with T = dt - dT: the reference schedule integrates T + dT, so the robot
         # advances exactly one knot dt per period, in step with the plan (period_final_time); the
         # dynamics are time-invariant, and a fixed interval keeps the step count the same in every
@@ -168,8 +264,12 @@ class ClosedLoop:
             st = self.stream if self.stream is not None else torch.cuda.current_stream()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(st)
-        h.fbd_euler_integrate_impedance(self.dm, self.state, self.imp, self.q_ref, 0.0, self.T,
-                                        self.dT, contacts=self.contacts, stream=self.stream)
+        if self.reference == "ik":   # slice by slice: joint_traj, nu_traj's joint rates, the lean term
+            h.fbd_euler_integrate_impedance_traj(self.dm, self.state, self.traj, 0.0, self.T, self.dT,
+                                                 contacts=self.contacts, stream=self.stream)
+        else:
+            h.fbd_euler_integrate_impedance(self.dm, self.state, self.imp, self.q_ref, 0.0, self.T,
+                                            self.dT, contacts=self.contacts, stream=self.stream)
         if ev is not None:
             e1.record(st)
             ev.append((e0, e1))
@@ -195,8 +295,15 @@ def split_groups(h, model, plan, states, groups, horizon=100, **kw):
     shared = ("knot_phase", "dt", "schedule")   # per-knot / scalar entries of the plan dict
     sl = lambda d, lo, hi: {k: (v if k in shared else v[lo:hi]) for k, v in d.items()}
     loops = []
+    ik = kw.pop("ik", None)
+    per_robot = ("se3_pose", "se3_twist", "com_pos", "com_vel", "joint_pos", "joint_vel")   # of ik["tasks"]
     for g in range(groups):
         stream = torch.cuda.Stream(device=h.device) if groups > 1 else None
+        if ik is not None:   # reference="ik": a given task set's per-robot arrays go with the group's robots
+            kw["ik"] = dict(ik)
+            if ik.get("tasks") is not None:
+                kw["ik"]["tasks"] = {k: (v[cut[g]:cut[g + 1]] if k in per_robot and v is not None else v)
+                                     for k, v in ik["tasks"].items()}
         loops.append(ClosedLoop(h, model, sl(plan, cut[g], cut[g + 1]), sl(states, cut[g], cut[g + 1]),
                                 horizon=horizon, stream=stream, **kw))
     return loops

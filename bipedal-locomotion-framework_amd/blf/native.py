@@ -32,7 +32,8 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance",
             "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate",
             "blf_fb_ik_solve_hard", "blf_fb_ik_integrate_hard", "blf_fb_ik_solve_limits",
-            "blf_fb_ik_integrate_limits", "blf_fb_ik_track"]
+            "blf_fb_ik_integrate_limits", "blf_fb_ik_track",
+            "blf_fbd_euler_integrate_impedance_traj", "blf_dcm_com_reference"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -74,6 +75,13 @@ class PostureLaw(ctypes.Structure):
 class JointImpedance(ctypes.Structure):
     """blf_joint_impedance: tau = kp (q_ref - q) - kd qdot before every Euler step."""
     _fields_ = [("ndof", _i32), ("reserved", _i32), ("kp", _vp), ("kd", _vp), ("q_ref", _vp)]
+
+
+class JointImpedanceTraj(ctypes.Structure):
+    """blf_joint_impedance_traj: the impedance with the reference indexed by the integration step."""
+    _fields_ = [("ndof", _i32), ("slices", _i32), ("steps_per_slice", _i32), ("reserved", _i32),
+                ("kp", _vp), ("kd", _vp), ("q_ref", _vp), ("qd_ref", _vp), ("qd_stride", _i64),
+                ("q_bias", _vp)]
 
 
 class SwingFootParams(ctypes.Structure):
@@ -237,6 +245,11 @@ def lib():
         L.blf_fbd_euler_integrate_impedance.argtypes = [
             _vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), ctypes.POINTER(JointImpedance),
             ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
+        L.blf_fbd_euler_integrate_impedance_traj.argtypes = [
+            _vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), ctypes.POINTER(JointImpedanceTraj),
+            ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
+        L.blf_dcm_com_reference.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _i64,
+                                            _vp, _vp, _vp, _vp]
         L.blf_fb_frame_state.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), _i32,
                                          _vp, _i64, _vp, _vp, _vp]
         L.blf_rls_advance.argtypes = [_vp, _i32, _i32, _f64, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
@@ -1337,3 +1350,75 @@ class Handle:
                 ctypes.byref(self._fb_contacts(contacts, B)), reg, B, float(t0), float(t1), float(dT))
         _check(lib().blf_fbd_euler_integrate_impedance(*args, _stream(stream)))
         return state
+
+    def joint_impedance_traj(self, impedance, q_ref, steps_per_slice, qd_ref=None, qd_offset=0, q_bias=None):
+        """A blf_joint_impedance_traj: impedance (joint_impedance()), q_ref [T,B,n] (fb_ik_track's
+        joint_traj), qd_ref [T,B,w] or None with the velocities at columns qd_offset .. qd_offset + n
+        (fb_ik_track's nu_traj with qd_offset = 6), q_bias [B,n] or None.  Returns an object with the
+        struct (.c) and the tensors (.t) it keeps alive."""
+        torch = _torch()
+
+        class _T:
+            pass
+        it = _T()
+        T, B, n = q_ref.shape
+        c = JointImpedanceTraj()
+        c.ndof, c.slices, c.steps_per_slice, c.reserved = n, T, int(steps_per_slice), 0
+        c.kp = _ptr(impedance["kp"], torch.float64, (n,), "kp")
+        c.kd = _ptr(impedance["kd"], torch.float64, (n,), "kd")
+        c.q_ref = _ptr(q_ref, torch.float64, (T, B, n), "q_ref")
+        it.t = dict(kp=impedance["kp"], kd=impedance["kd"], q_ref=q_ref, qd_ref=qd_ref, q_bias=q_bias)
+        if qd_ref is not None:
+            w = qd_ref.shape[-1]
+            _ptr(qd_ref, torch.float64, (T, B, w), "qd_ref")
+            if not 0 <= qd_offset <= w - n:
+                raise ValueError(f"qd_ref: columns {qd_offset}..{qd_offset + n} outside [0, {w})")
+            c.qd_ref, c.qd_stride = _vp(qd_ref.data_ptr() + 8 * int(qd_offset)), w
+        if q_bias is not None:
+            c.q_bias = _ptr(q_bias, torch.float64, (B, n), "q_bias")
+        it.c, it.batch = c, B
+        return it
+
+    def fbd_euler_integrate_impedance_traj(self, dm, state, traj, t0, t1, dT, contacts=None, mass_reg=None,
+                                           stream=None):
+        """blf_fbd_euler_integrate_impedance_traj in place on `state`: integration step i tracks slice
+        min(i // steps_per_slice, T - 1) of traj (joint_impedance_traj()),
+        tau = kp (q_ref + q_bias - q) - kd (qdot - qd_ref)."""
+        torch = _torch()
+        B, n = state["joint_pos"].shape
+        NV = n + 6
+        if traj.batch != B:
+            raise ValueError(f"the trajectory holds {traj.batch} robots, the state {B}")
+        reg = _ptr(mass_reg, torch.float64, (NV, NV), "mass_reg") if mass_reg is not None else None
+        args = (self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(traj.c),
+                ctypes.byref(self._fb_contacts(contacts, B)), reg, B, float(t0), float(t1), float(dT))
+        _check(lib().blf_fbd_euler_integrate_impedance_traj(*args, _stream(stream)))
+        return state
+
+    def dcm_com_reference(self, xi0, vrp, omega, z_ref, c_ref, steps, dT, column=0, com_pos=None, com_vel=None,
+                          xi_end=None, stream=None):
+        """blf_dcm_com_reference: the CoM set points com_pos, com_vel [B,T,3] of an ik_schedule from the
+        measured DCM xi0 [B,2] (fb_dcm), the plan's first VRP (vrp [B,N,2], a solve's output) and
+        omega[:, column] ([B,K]); z_ref [B]; c_ref [B,2] is read and advanced in place.  xi_end [B,2]:
+        None allocates, False leaves it out.  Returns (com_pos, com_vel, xi_end)."""
+        torch = _torch()
+        B, N = vrp.shape[0], vrp.shape[1]
+        K = omega.shape[1]
+        dev = vrp.device
+        T = int(steps)
+        _ptr(omega, torch.float64, (B, K), "omega")
+        if not 0 <= column < K:
+            raise ValueError(f"omega column {column} outside [0, {K})")
+        new = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        com_pos = com_pos if com_pos is not None else new((B, max(T, 0), 3))
+        com_vel = com_vel if com_vel is not None else new((B, max(T, 0), 3))
+        if xi_end is None:
+            xi_end = new((B, 2))
+        shp = (B, max(T, 0), 3)
+        _check(lib().blf_dcm_com_reference(
+            self._h, _ptr(xi0, torch.float64, (B, 2), "xi0"), _ptr(vrp, torch.float64, (B, N, 2), "vrp"), 2 * N,
+            _vp(omega.data_ptr() + 8 * column), K, _ptr(z_ref, torch.float64, (B,), "z_ref"),
+            _ptr(c_ref, torch.float64, (B, 2), "c_ref"), T, float(dT), B,
+            _ptr(com_pos, torch.float64, shp, "com_pos"), _ptr(com_vel, torch.float64, shp, "com_vel"),
+            _ptr(xi_end, torch.float64, (B, 2), "xi_end") if xi_end is not False else None, _stream(stream)))
+        return com_pos, com_vel, (xi_end if xi_end is not False else None)

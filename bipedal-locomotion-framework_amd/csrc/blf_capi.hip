@@ -804,6 +804,54 @@ blf_status blf_fbd_euler_integrate_impedance(blf_handle* handle, const blf_fb_mo
                             dT_last, (hipStream_t)stream, impedance);
 }
 
+blf_status blf_fbd_euler_integrate_impedance_traj(blf_handle* handle, const blf_fb_model* model,
+                                                  const blf_fb_state* state,
+                                                  const blf_joint_impedance_traj* impedance,
+                                                  const blf_fb_contacts* contacts,
+                                                  const double* mass_reg, int64_t batch,
+                                                  double initial_time, double final_time, double dT,
+                                                  void* stream)
+{
+    const char* fn = "blf_fbd_euler_integrate_impedance_traj";
+    BLF_REQUIRE(impedance != nullptr, "%s: null impedance", fn);
+    BLF_REQUIRE(impedance->reserved == 0, "%s: reserved must be 0", fn);
+    BLF_REQUIRE(impedance->slices >= 1 && impedance->steps_per_slice >= 1,
+                "%s: slices=%d, steps_per_slice=%d, both must be >= 1", fn, impedance->slices,
+                impedance->steps_per_slice);
+    BLF_REQUIRE(impedance->kp && impedance->kd && (batch == 0 || impedance->q_ref),
+                "%s: null impedance array", fn);
+    BLF_REQUIRE(model != nullptr && impedance->ndof == model->ndof, "%s: impedance ndof %d != model ndof %d",
+                fn, impedance->ndof, model ? model->ndof : -1);
+    BLF_REQUIRE(impedance->qd_ref == nullptr || impedance->qd_stride >= impedance->ndof,
+                "%s: qd_stride=%lld below ndof=%d", fn, (long long)impedance->qd_stride, impedance->ndof);
+    // the constant-torque checks with a stand-in torque pointer (the impedance replaces it)
+    blf_status st = check_fbd(fn, handle, model, state, impedance->kp, contacts, batch);
+    if (st != BLF_OK) return st;
+    int iterations = 0;
+    double dT_last = 0.0;
+    st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
+    if (st != BLF_OK) return st;
+    return launch_fbd_euler_traj(model, state, contacts, mass_reg, batch, iterations, dT, dT_last,
+                                 (hipStream_t)stream, impedance);
+}
+
+blf_status blf_dcm_com_reference(blf_handle* handle, const double* xi0, const double* vrp,
+                                 int64_t vrp_stride, const double* omega0, int64_t omega0_stride,
+                                 const double* z_ref, double* c_ref, int32_t steps, double dT,
+                                 int64_t batch, double* com_pos, double* com_vel, double* xi_end,
+                                 void* stream)
+{
+    BLF_REQUIRE(handle != nullptr, "blf_dcm_com_reference: null handle");
+    BLF_REQUIRE(steps >= 1, "blf_dcm_com_reference: steps=%d, must be >= 1", steps);
+    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_dcm_com_reference: dT=%g, must be finite and positive", dT);
+    BLF_REQUIRE(batch >= 0 && vrp_stride >= 2 && omega0_stride >= 0,
+                "blf_dcm_com_reference: bad batch / vrp stride / omega0 stride");
+    BLF_REQUIRE(batch == 0 || (xi0 && vrp && omega0 && z_ref && c_ref && com_pos && com_vel),
+                "blf_dcm_com_reference: null buffer");
+    return launch_com_reference(xi0, vrp, vrp_stride, omega0, omega0_stride, z_ref, c_ref, steps, dT, batch,
+                                com_pos, com_vel, xi_end, (hipStream_t)stream);
+}
+
 blf_status blf_fbd_euler_integrate(blf_handle* handle, const blf_fb_model* model,
                                    const blf_fb_state* state, const double* joint_torque,
                                    const blf_fb_contacts* contacts, const double* mass_reg,

@@ -137,6 +137,12 @@ blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, cons
                             const blf_fb_contacts* ct, const double* reg, int64_t batch,
                             int32_t nsteps, double dT, double dT_last, hipStream_t s,
                             const blf_joint_impedance* impedance = nullptr);
+blf_status launch_fbd_euler_traj(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
+                                 const double* reg, int64_t batch, int32_t nsteps, double dT, double dT_last,
+                                 hipStream_t s, const blf_joint_impedance_traj* impedance);
+blf_status launch_com_reference(const double* xi0, const double* vrp, int64_t vstride, const double* omega0,
+                                int64_t ostride, const double* zref, double* cref, int32_t T, double dT,
+                                int64_t batch, double* cpos, double* cvel, double* xiend, hipStream_t s);
 size_t fbd_lds_bytes(int n, int C, bool aba = false);   // aba: the articulated-body layout
 blf_status launch_fb_dcm(const blf_fb_model* md, const blf_fb_state* st, const double* omega0,
                          int64_t ostride, int64_t batch, double* com, double* xi, hipStream_t s);

@@ -916,6 +916,178 @@ __global__ __launch_bounds__(256) void posture_reference_kernel(int n, const dou
     qref[e] = (qnom[j] + lean[2 * j] * ex) + lean[2 * j + 1] * ey;
 }
 
+// The closed loop's plan -> CoM reference map (blf_dcm_com_reference, blf_c.h section 9b): the
+// LIP's stable half integrated under the plan's first VRP, T explicit Euler steps of h.  Lane per
+// (system, horizontal axis); the axis-0 lane also writes the height column.  A system with a
+// non-finite input writes NaN to every output of its own.
+__global__ __launch_bounds__(256) void com_reference_kernel(const double* __restrict__ xi0,
+                                                            const double* __restrict__ vrp, int64_t vstride,
+                                                            const double* __restrict__ omega0, int64_t ostride,
+                                                            const double* __restrict__ zref, double* __restrict__ cref,
+                                                            int32_t T, double h, int64_t batch,
+                                                            double* __restrict__ cpos, double* __restrict__ cvel,
+                                                            double* __restrict__ xiend)
+{
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 2 * batch) return;
+    const int64_t q = e >> 1;
+    const int a = (int)(e & 1);
+    const double w = omega0[q * ostride], z = zref[q];
+    auto fin = [](double x) { return __builtin_isfinite(x); };
+    // (a system's two lanes sit in one wavefront: both read cref here before either writes it below)
+    const bool ok = fin(xi0[2 * q]) && fin(xi0[2 * q + 1]) && fin(vrp[q * vstride]) && fin(vrp[q * vstride + 1]) &&
+                    fin(w) && fin(z) && fin(cref[2 * q]) && fin(cref[2 * q + 1]);
+    const double nan = __builtin_nan("");
+    const double nwr = -w * vrp[q * vstride + a];
+    double xi = ok ? xi0[2 * q + a] : nan, c = ok ? cref[2 * q + a] : nan;
+    double* p = cpos + 3 * (int64_t)T * q;
+    double* v = cvel + 3 * (int64_t)T * q;
+    for (int32_t t = 0; t < T; ++t) {
+        const double vt = w * (xi - c);
+        p[3 * t + a] = c;
+        v[3 * t + a] = vt;
+        if (a == 0) {
+            p[3 * t + 2] = ok ? z : nan;
+            v[3 * t + 2] = ok ? 0.0 : nan;
+        }
+        c = c + vt * h;
+        xi = xi + ((w * xi) + nwr) * h;
+    }
+    cref[2 * q + a] = c;
+    if (xiend) xiend[2 * q + a] = xi;
+}
+
+// blf_fbd_euler_integrate_impedance_traj: fbd_euler_kernel's impedance form with the reference
+// indexed by the integration step, slice s(i) = min(i / sps, T - 1) of qref [T][B][n], a velocity
+// feed-forward qdref (or null) and a per-system bias qbias (or null):
+//   r = qref (+ qbias),  tau = kp (r - q) - kd (qdot - qdref)   (qdref null: - kd qdot)
+struct ImpedanceTraj {
+    const double *kp, *kd, *qref, *qdref, *qbias;
+    int64_t qdstride;
+    int32_t T, sps;
+};
+
+// Text of its own beside fbd_euler_kernel (whose instantiations keep their assembly): the same
+// staging, step and write-back, and the torque block replaced.  Two systems per wavefront: r and
+// qdref of the current slice sit in LDS (r in Smem's q_ref slot, qdref in n doubles behind
+// Smem::total) and are restaged only at a step where the slice changes; one system per wavefront
+// reads them from global memory every step, as the held form reads imp.qref.
+template <int NVMAX, int HW, bool PRI, bool ABA>
+__global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_traj_kernel(Model m, blf_fb_state st,
+                                                          Contacts ct, const double* reg,
+                                                          int32_t nsteps, double dT, double dT_last,
+                                                          ImpedanceTraj imp, int64_t batch)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const Half<HW> H;
+    const int n = m.n, NV = n + 6;
+    constexpr bool kCS = HW == 32;
+    const int nx = kCS ? (n + 1) & ~1 : 0;   // the slice's qdref behind the system's Smem block
+    const Smem S(smem + H.half * (Smem(nullptr, n, ct.C, ABA).total + nx), n, ct.C, ABA);
+    double* const qdr = S.base + S.total;
+    const int lane = H.hl;
+    constexpr int per = kWave / HW;
+    const Topo T = build_topo<HW>(m, S);
+    double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n | dR 9
+    double* dR = loc + 18 + 2 * n;
+    const int64_t i0 = (int64_t)blockIdx.x * per + H.half;
+    const bool active = i0 < batch;   // see fbd_euler_kernel
+    const int64_t q = active ? i0 : batch - 1;
+    for (int i = lane; i < 18 + 2 * n; i += HW) {
+        double v;
+        if (i < 6) v = st.base_vel[6 * q + i];
+        else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
+        else if (i < 9 + n) {   // the reference point; the position relative to it starts at zero
+            loc[kRef(n) + (i - 6 - n)] = st.base_pos[3 * q + (i - 6 - n)];
+            v = 0.0;
+        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
+        loc[i] = v;
+    }
+    if constexpr (kCS) {
+        const int C = ct.C;
+        for (int i = lane; i < 29 * C; i += HW) {
+            double v;
+            if (i < C) v = (double)m.flink[ct.frame[i]];
+            else if (i < 13 * C) v = m.fpose[12 * ct.frame[(i - C) / 12] + (i - C) % 12];
+            else if (i < 25 * C) {   // null poses, their positions relative to the reference point
+                const int e = (i - 13 * C) % 12;
+                v = ct.null_pose[(q * C) * 12 + (i - 13 * C)];
+                if (e < 3) v = v - st.base_pos[3 * q + e];
+            }
+            else v = ct.params[i - 25 * C];
+            S.cst()[i] = v;
+        }
+        for (int j = lane; j < n; j += HW) {
+            S.imp()[j] = imp.kp[j];
+            S.imp()[n + j] = imp.kd[j];
+        }
+    }
+    wave_sync();
+    bool ok = true;
+    int32_t slice = -1, left = 0;   // the slice in use and the steps it still holds
+    for (int32_t step = 0; step < nsteps; ++step) {
+        const double h = step + 1 < nsteps ? dT : dT_last;
+        const bool next = left == 0 && slice + 1 < imp.T;   // the last slice is held to the end
+        if (next) {
+            ++slice;
+            left = imp.sps;
+        }
+        --left;
+        const int64_t at = (int64_t)slice * batch + q;   // element (slice, q, .)
+        if constexpr (kCS) {
+            if (next)
+                for (int j = lane; j < n; j += HW) {
+                    double r = imp.qref[at * n + j];
+                    if (imp.qbias) r = r + imp.qbias[(int64_t)n * q + j];
+                    S.imp()[2 * n + j] = r;
+                    if (imp.qdref) qdr[j] = imp.qdref[at * imp.qdstride + j];
+                }
+        }
+        // the control input of this step from its start state
+        for (int j = lane; j < n; j += HW) {
+            if constexpr (kCS) {
+                if (imp.qdref)
+                    S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * (loc[6 + j] - qdr[j]);
+                else
+                    S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * loc[6 + j];
+            } else {
+                double r = imp.qref[at * n + j];
+                if (imp.qbias) r = r + imp.qbias[(int64_t)n * q + j];
+                if (imp.qdref)
+                    S.tq()[j] = imp.kp[j] * (r - loc[18 + n + j]) - imp.kd[j] * (loc[6 + j] - imp.qdref[at * imp.qdstride + j]);
+                else
+                    S.tq()[j] = imp.kp[j] * (r - loc[18 + n + j]) - imp.kd[j] * loc[6 + j];
+            }
+        }
+        wave_sync();
+        ok = fbd_eval<NVMAX, HW, PRI, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
+                                                S.tq(), ct, q, reg, T, loc + kRef(n)) && ok;
+        if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, loc + 3, dR);
+        wave_sync();
+        // positions first (they read the old velocities), then the velocities: fbd_euler_kernel
+        for (int i = lane; i < 12 + n; i += HW) {
+            if (i < 3) loc[6 + n + i] = loc[6 + n + i] + loc[i] * h;
+            else if (i < 12) loc[6 + n + i] = loc[6 + n + i] + dR[i - 3] * h;
+            else loc[18 + n + (i - 12)] = loc[18 + n + (i - 12)] + loc[6 + (i - 12)] * h;
+        }
+        wave_sync();
+        for (int i = lane; i < NV; i += HW) loc[i] = loc[i] + S.rhs()[i] * h;
+        wave_sync();
+    }
+    if (active) {
+        const double nan = __builtin_nan("");
+        for (int i = lane; i < 18 + 2 * n; i += HW) {
+            const double v = ok ? loc[i] : nan;
+            if (i < 6) st.base_vel[6 * q + i] = v;
+            else if (i < 6 + n) st.joint_vel[(int64_t)n * q + (i - 6)] = v;
+            else if (i < 9 + n) st.base_pos[3 * q + (i - 6 - n)] = loc[kRef(n) + (i - 6 - n)] + v;
+            else if (i < 18 + n) st.base_rot[9 * q + (i - 9 - n)] = v;
+            else st.joint_pos[(int64_t)n * q + (i - 18 - n)] = v;
+        }
+    }
+}
+
 Contacts to_contacts(const blf_fb_contacts* c)
 {
     Contacts o;
@@ -984,6 +1156,40 @@ blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, cons
                            to_model(md), *st, tau, c, reg, nsteps, dT, dT_last, imp, batch);
 #undef FBD_EUL
     return check_hip(hipGetLastError(), "fbd_euler_kernel launch");
+}
+
+blf_status launch_fbd_euler_traj(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
+                                 const double* reg, int64_t batch, int32_t nsteps, double dT, double dT_last,
+                                 hipStream_t s, const blf_joint_impedance_traj* it)
+{
+    if (batch == 0) return BLF_OK;
+    const Contacts c = to_contacts(ct);
+    const ImpedanceTraj imp{it->kp, it->kd, it->q_ref, it->qd_ref, it->q_bias, it->qd_stride, it->slices,
+                            it->steps_per_slice};
+    const bool pri = md->joint_type != nullptr, aba = use_aba(reg);
+    const size_t lds = fbd_lds_bytes(md->ndof, c.C, aba);
+    // two systems per wavefront: the slice's qdref behind each system's block (the kernel's nx)
+    const size_t ext = sizeof(double) * (size_t)((md->ndof + 1) & ~1);
+#define FBD_TRJ(NV, HW) (pri ? (aba ? fbd_euler_traj_kernel<NV, HW, true, true> : fbd_euler_traj_kernel<NV, HW, true, false>) \
+                             : (aba ? fbd_euler_traj_kernel<NV, HW, false, true> : fbd_euler_traj_kernel<NV, HW, false, false>))
+    if (md->ndof + 6 <= 32)
+        hipLaunchKernelGGL(FBD_TRJ(32, 32), dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * (lds + ext), s,
+                           to_model(md), *st, c, reg, nsteps, dT, dT_last, imp, batch);
+    else
+        hipLaunchKernelGGL(FBD_TRJ(BLF_FBD_MAX_DOFS + 6, kWave), dim3((unsigned)batch), dim3(kWave), lds, s,
+                           to_model(md), *st, c, reg, nsteps, dT, dT_last, imp, batch);
+#undef FBD_TRJ
+    return check_hip(hipGetLastError(), "fbd_euler_traj_kernel launch");
+}
+
+blf_status launch_com_reference(const double* xi0, const double* vrp, int64_t vstride, const double* omega0,
+                                int64_t ostride, const double* zref, double* cref, int32_t T, double dT,
+                                int64_t batch, double* cpos, double* cvel, double* xiend, hipStream_t s)
+{
+    if (batch == 0) return BLF_OK;
+    hipLaunchKernelGGL(com_reference_kernel, dim3((unsigned)ceil_div(2 * batch, 256)), dim3(256), 0, s, xi0, vrp,
+                       vstride, omega0, ostride, zref, cref, T, dT, batch, cpos, cvel, xiend);
+    return check_hip(hipGetLastError(), "com_reference_kernel launch");
 }
 
 blf_status launch_fb_dcm(const blf_fb_model* md, const blf_fb_state* st, const double* omega0,

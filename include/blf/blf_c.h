@@ -46,6 +46,10 @@
  *                             closed loop (config 5); no reference counterpart
  *   blf_fbd_euler_integrate_impedance  blf_fbd_euler_integrate with a joint impedance as the
  *                             control input of every step (the user's per-step setControlInput)
+ *   blf_fbd_euler_integrate_impedance_traj / blf_dcm_com_reference  the same with the reference
+ *                             indexed by the step (a joint trajectory followed in one launch), and
+ *                             the plan -> CoM set point map that feeds blf_fb_ik_track; no reference
+ *                             counterpart
  *   blf_dcm_mpc_solve[_warm]  ABSENT in the reference (TimeVaryingDCMPlanner QP),
  *                             driven through System/Advanceable.h:24-46 (advance()) by the C++ host
  *                             adapter blf::Planners::TimeVaryingDCMPlanner
@@ -98,7 +102,8 @@ const char* blf_last_error(void);
  * is additive: it adds blf_rls_advance and blf_contact_rls_advance and changes no existing entry
  * point or struct.  blf_swing_foot_eval and blf_so3_eval, and later blf_fb_ik_solve_hard and
  * blf_fb_ik_integrate_hard (section 12b), then blf_fb_ik_solve_limits and
- * blf_fb_ik_integrate_limits (section 12c), then blf_fb_ik_track (section 12d), were added within ABI 3 (no existing
+ * blf_fb_ik_integrate_limits (section 12c), then blf_fb_ik_track (section 12d), then blf_fbd_euler_integrate_impedance_traj
+ * (section 9) and blf_dcm_com_reference (section 9b), were added within ABI 3 (no existing
  * entry point or struct changed, so the number stays): a caller detects them by symbol
  * (dlsym).  ABI 2 (0.2.0) added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
  * a caller built against an older header must zero-initialise these structs (`= {0}`), since the
@@ -569,6 +574,64 @@ blf_status blf_fbd_euler_integrate_impedance(blf_handle* handle, const blf_fb_mo
                                              const double* mass_reg, int64_t batch,
                                              double initial_time, double final_time, double dT,
                                              void* stream);
+/* blf_fbd_euler_integrate_impedance_traj: blf_fbd_euler_integrate_impedance with the reference
+ * indexed by the integration step, a velocity feed-forward and a per-robot bias, so that a joint
+ * trajectory (blf_fb_ik_track's joint_traj / nu_traj as they stand) is followed in one launch.  The
+ * schedule is blf_step_schedule's, unchanged (the stale last step included).  Integration step i of
+ * the call (0-based) uses slice
+ *   s(i) = min(i / steps_per_slice, slices - 1)        (integer division; the last slice is held)
+ * and, with r_j = q_ref[s][b][j] + q_bias[b][j] (q_bias NULL: r_j = q_ref[s][b][j], no addition),
+ *   tau_j = kp_j (r_j - q_j) - kd_j (qdot_j - qd_ref[s][b][j])      (qd_ref NULL: - kd_j qdot_j,
+ * the expression of blf_fbd_euler_integrate_impedance: with qd_ref and q_bias NULL and identical
+ * slices the call equals that one bit for bit).  Slices past the last one used are never read.  A
+ * non-finite reference of robot b gives that robot a NaN state and touches no other robot.
+ * BLF_ERR_INVALID_ARGUMENT: what blf_fbd_euler_integrate_impedance refuses, slices < 1,
+ * steps_per_slice < 1, reserved != 0, qd_stride < n with qd_ref set, ndof != the model's.           */
+typedef struct blf_joint_impedance_traj {
+    int32_t ndof;                 /* n, must match the model                                 */
+    int32_t slices;               /* T >= 1                                                  */
+    int32_t steps_per_slice;      /* >= 1                                                    */
+    int32_t reserved;             /* must be 0                                               */
+    const double* kp;             /* [n]                                                     */
+    const double* kd;             /* [n]                                                     */
+    const double* q_ref;          /* [T][B][n]: blf_fb_ik_track's joint_traj as it stands    */
+    const double* qd_ref;         /* element (t,b,j) at qd_ref[(t*B + b)*qd_stride + j], or NULL
+                                     (zero): nu_traj + 6 with qd_stride = 6 + n              */
+    int64_t qd_stride;            /* >= n when qd_ref                                        */
+    const double* q_bias;         /* [B][n] or NULL: added to every slice                    */
+} blf_joint_impedance_traj;
+blf_status blf_fbd_euler_integrate_impedance_traj(blf_handle* handle, const blf_fb_model* model,
+                                                  const blf_fb_state* state,
+                                                  const blf_joint_impedance_traj* impedance,
+                                                  const blf_fb_contacts* contacts,
+                                                  const double* mass_reg, int64_t batch,
+                                                  double initial_time, double final_time, double dT,
+                                                  void* stream);
+
+/* ---- 9b. Closed loop: the plan -> centre-of-mass reference map ---------------------------------
+ * blf_dcm_com_reference: the set points blf_ik_schedule reads (com_pos, com_vel [B][T][3]) from a
+ * solved DCM window: the LIP's stable half cdot = omega (xi - c) integrated by T explicit Euler
+ * steps of dT under the plan's first VRP r0 = vrp[b * vrp_stride + (0, 1)], held over the period,
+ * with omega = omega0[b * omega0_stride].  Per robot b and horizontal axis a, in this order:
+ *   xi_0 = xi0[b][a],  c_0 = c_ref[b][a],  nwr = -omega * r0_a
+ *   for t = 0 .. T-1:
+ *     v_t = omega * (xi_t - c_t)
+ *     com_pos[b][t] = (c_t[0], c_t[1], z_ref[b]),  com_vel[b][t] = (v_t[0], v_t[1], 0)
+ *     c_{t+1}  = c_t + v_t * dT
+ *     xi_{t+1} = xi_t + ((omega * xi_t) + nwr) * dT                      (section 2's step)
+ *   c_ref[b][a] = c_T (in place: the reference carries over to the next period; feedback enters
+ *   through xi0 only),  xi_end[b][a] = xi_T when xi_end is given.
+ * xi0 [B][2] (blf_fb_dcm's xi), z_ref [B], c_ref [B][2], xi_end [B][2] or NULL.  A robot with a
+ * non-finite xi0, r0, omega, z_ref or c_ref gets NaN in every output of its own (com_pos, com_vel,
+ * c_ref, xi_end); no other robot is touched.  NULL handle or buffer (batch > 0), steps < 1, a dT
+ * that is not finite and positive, vrp_stride < 2 or a negative omega0_stride or batch:
+ * BLF_ERR_INVALID_ARGUMENT, nothing written; batch == 0: BLF_OK.                                 */
+blf_status blf_dcm_com_reference(blf_handle* handle, const double* xi0, const double* vrp,
+                                 int64_t vrp_stride, const double* omega0, int64_t omega0_stride,
+                                 const double* z_ref, double* c_ref, int32_t steps, double dT,
+                                 int64_t batch, double* com_pos, double* com_vel, double* xi_end,
+                                 void* stream);
+
 /* ---- 10. Recursive least squares (Estimators::RecursiveLeastSquare), batched ------------------
  * B independent filters, each with state x (n), covariance P (n x n), forgetting factor lambda and
  * a diagonal measurement covariance R = diag(r) (m).  One step with regressor H (m x n) and

@@ -29,6 +29,14 @@ warm-up, median of `rounds` rounds, the variants alternating within a round.  On
     so the ratio is the track kernel's own overhead); and the unfused route to per-step set
     points a user had before, `steps` x { blf_fb_ik_solve_limits with step t's set points and that
     uniform mask; blf_fbk_euler_integrate }.
+  * with --closed-loop, instead of the above: blf_fbd_euler_integrate_impedance_traj on B standing
+    humanoids over 19 steps of 1 ms, (a) with 4 identical slices and neither qd_ref nor q_bias against
+    blf_fbd_euler_integrate_impedance with that reference (the same arithmetic, bit for bit: the ratio
+    is the cost of the slice logic) and (b) with 4 distinct slices, qd_ref and q_bias; then (c) one
+    period of blf.closed_loop.ClosedLoop(reference="ik") against one posture-mode period, both over
+    two stream groups (events from the first launch to each group's last, the slower group counts),
+    and blf_dcm_com_reference, blf_fb_ik_track and the trajectory dynamics each alone at B robots as
+    shares of the IK period (the groups overlap, so the shares need not add up to 1).
 
 Counted flops per robot-step, NV = n + 6, M = the task rows of non-zero weight: H and g from the task
 rows M (NV (NV + 1) + 2 NV), the Cholesky factorization NV^3 / 3, the two substitutions 2 NV^2.  The
@@ -38,6 +46,7 @@ includes one stream synchronisation: the unfused sequence pays 20 of them, the f
 
   timeout -k 10 600 python tools/ik_bench.py [--robots 16384] [--steps 20] [--rounds 5] [--hard] [--limits]
   timeout -k 10 600 python tools/ik_bench.py --track [--robots 16384] [--steps 20] [--rounds 5]
+  timeout -k 10 600 python tools/ik_bench.py --closed-loop [--robots 16384] [--rounds 5] [--reps 3]
 (BLF_LIB=.../lib/libblf_<name>.so times a variant build, tools/build_variant.sh)
 """
 import argparse
@@ -191,8 +200,113 @@ def track_bench(h, args):
                       "label": args.label}), flush=True)
 
 
+def closed_loop_bench(h, args):
+    """--closed-loop: the trajectory impedance against the held-reference call, and one IK-mode period of
+    blf.closed_loop.ClosedLoop against one posture-mode period (two stream groups)."""
+    from blf import closed_loop as DL, problems as P
+    B, T = args.robots, 4
+    model = robot.humanoid24()
+    n = model["n"]
+    host = robot.standing_states(model, B, seed=3)
+    law = robot.posture_law_arrays(model)
+    dev = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).cuda()
+    dm = h.fb_model(model)
+    start = {k: dev(host[k]) for k in native.FB_STATE_KEYS}
+    st = {k: v.clone() for k, v in start.items()}
+    contacts = dict(frame=dev(np.arange(2), torch.int32), params=dev(np.tile(np.asarray(DL.CONTACT_PARAMS), (2, 1))),
+                    null_pose=dev(robot.sole_null_poses(model, host)))
+    imp = h.joint_impedance(law["kp"], law["kd"])
+    rng = np.random.default_rng(4)
+    q0 = dev(rng.normal(size=(B, n)) * 0.02)
+    same = h.joint_impedance_traj(imp, q0[None].expand(T, -1, -1).contiguous(), 5)
+    full = h.joint_impedance_traj(imp, dev(rng.normal(size=(T, B, n)) * 0.02), 5,
+                                  qd_ref=dev(rng.uniform(-0.1, 0.1, (T, B, 6 + n))), qd_offset=6,
+                                  q_bias=dev(rng.uniform(-0.01, 0.01, (B, n))))
+    t1, dT = 0.019, 0.001   # 19 steps: one control period of the closed loop
+
+    def restore():
+        for k in native.FB_STATE_KEYS:
+            st[k].copy_(start[k])
+
+    def held():
+        restore()
+        h.fbd_euler_integrate_impedance(dm, st, imp, q0, 0.0, t1, dT, contacts=contacts)
+
+    def traj(tr):
+        restore()
+        h.fbd_euler_integrate_impedance_traj(dm, st, tr, 0.0, t1, dT, contacts=contacts)
+
+    res = compare({"restore": restore, "held": held, "traj_same": lambda: traj(same), "traj_full": lambda: traj(full)},
+                  reps=args.reps, rounds=args.rounds)
+    held()
+    a = st["joint_vel"].clone()
+    traj(same)
+    r0 = res["restore"][0]
+    net = {k: res[k][0] - r0 for k in ("held", "traj_same", "traj_full")}
+    print(json.dumps({"bench": "impedance_traj", "robots": B, "steps": 19, "slices": T, "held_ms": res["held"],
+                      "traj_identical_slices_ms": res["traj_same"], "traj_distinct_qd_bias_ms": res["traj_full"],
+                      "restore_ms": res["restore"], "traj_identical_over_held_net": net["traj_same"] / net["held"],
+                      "traj_distinct_over_held_net": net["traj_full"] / net["held"],
+                      "traj_identical_equals_held_bitwise": torch.equal(a, st["joint_vel"]),
+                      "label": args.label}), flush=True)
+    # one period of the loop, both modes, two stream groups; reps periods per timing
+    periods = 3 + args.rounds * args.reps
+    plan = P.make_batch(B, horizon=100 + periods, n_footsteps=8, seed=P.SEED, first_ds=periods + 10)
+    loops = {m: DL.split_groups(h, model, plan, host, 2, reference=m) for m in ("posture", "ik")}
+
+    def run(mode, reps):
+        torch.cuda.synchronize()
+        e0 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for g in loops[mode]:
+            g.stream.wait_event(e0)
+        for _ in range(reps):
+            for g in loops[mode]:
+                g.period()
+        ends = []
+        for g in loops[mode]:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(g.stream)
+            ends.append(e)
+        torch.cuda.synchronize()
+        return max(e0.elapsed_time(e) for e in ends) / reps
+
+    for m in loops:
+        run(m, 3)
+    times = {m: [] for m in loops}
+    for _ in range(args.rounds):
+        for m in loops:
+            times[m].append(run(m, args.reps))
+    med = {m: [statistics.median(v), min(v), max(v)] for m, v in times.items()}
+    # the IK period's own pieces, each alone on the default stream at all B robots (the loop's buffers)
+    one = DL.ClosedLoop(h, model, plan, host, reference="ik")
+    one.period()
+    out = one.bufs[0]
+    pieces = compare({
+        "com_reference": lambda: h.dcm_com_reference(one.xi, out["vrp"], one.omega, one.z_ref, one.c_ref, one.ik_steps,
+                                                     one.ik_dT, column=1, com_pos=one.com_pos, com_vel=one.com_vel,
+                                                     xi_end=one.xi_end),
+        "fb_ik_track": lambda: h.fb_ik_track(one.dm, one.ik_state, one.ik_tasks, one.ik_schedule, one.ik_dT,
+                                             hard=one.ik_hard, limits=one.ik_limits, joint_traj=one.joint_traj,
+                                             base_traj=False, nu_traj=one.nu_traj, status=one.ik_status,
+                                             fail_step=one.ik_fail_step, iters=one.ik_iters, active=one.ik_active),
+        "dynamics_traj": lambda: h.fbd_euler_integrate_impedance_traj(one.dm, one.state, one.traj, 0.0, one.T, one.dT,
+                                                                      contacts=one.contacts)},
+        reps=1, rounds=args.rounds)
+    ik_ok = all(bool((g.ik_status == 0).all()) for g in loops["ik"])
+    finite = all(bool(torch.isfinite(g.state["joint_pos"]).all()) for g in loops["ik"])
+    print(json.dumps({"bench": "closed_loop_ik_period", "robots": B, "groups": 2, "periods_per_mode": periods,
+                      "posture_period_ms": med["posture"], "ik_period_ms": med["ik"],
+                      "ik_over_posture": med["ik"][0] / med["posture"][0],
+                      "alone_ms": {k: v for k, v in pieces.items()},
+                      "share_of_ik_period": {k: v[0] / med["ik"][0] for k, v in pieces.items()},
+                      "all_ik_status_ok": ik_ok, "states_finite": finite, "label": args.label}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--closed-loop", action="store_true",
+                    help="time the trajectory impedance and the closed loop's IK period instead")
     ap.add_argument("--robots", type=int, default=16384)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
@@ -209,8 +323,8 @@ def main():
     print(json.dumps({"bench": "provenance", "lib_src_hash": prov["lib_src_hash"],
                       "lib": os.path.basename(prov["lib"]), "matches_tree": prov["matches"],
                       "device": torch.cuda.get_device_name(0), "label": args.label}), flush=True)
-    if args.track:
-        track_bench(h, args)
+    if args.track or args.closed_loop:
+        (closed_loop_bench if args.closed_loop else track_bench)(h, args)
         h.close()
         return
     B, steps = args.robots, args.steps
