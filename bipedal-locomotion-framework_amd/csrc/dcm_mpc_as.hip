@@ -27,6 +27,8 @@
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace blf {
 namespace {
 using namespace qp;
@@ -149,6 +151,37 @@ __device__ __forceinline__ Row<T> normal(const RS& R, int i, int col)
 {
     const auto a = R.A2[R.at(i, col)];
     return {T(a.x), T(a.y), T(0)};
+}
+
+// The fp32 search's rows in registers (8 facet slots): every row of the lane's knots, read from
+// the fp64 LDS table and rounded once after the staging commit, instead of once per float pass
+// (as_certify's feasibility scan: per knot and pass 8 ds_read and 12 v_cvt_f32_f64 at four
+// facets) and once more in as_guess.  3 x 8 x KPL VGPRs, which the float phase has free (the fp64
+// passes set the kernels' register count).  Slots i >= M of the launch and the slots of a lane
+// without a knot hold row 0 of column 0 (in bounds; never used); slots m <= i < M hold whatever
+// the caller left in A / b, and every reader masks them by the knot's count.  NoRows: the reader
+// takes the rows from LDS (the fp64 passes; the 16-slot and the phase-indexed instances).
+struct NoRows {};
+template <int KPL>
+struct RegRows {
+    Row<float> v[KPL][kMaxFacets];
+};
+template <class RR>
+constexpr bool kHasRows = !std::is_same<RR, NoRows>::value;
+
+template <int KPL, class RS>
+__device__ __forceinline__ void load_rows(RegRows<KPL>& rr, const RS& R, int N, int M, int lane)
+{
+#pragma unroll
+    for (int j = 0; j < KPL; ++j) {
+        const int col = KPL * lane + j < N ? R.col(j, lane) : 0;
+#pragma unroll
+        for (int i = 0; i < kMaxFacets; ++i) rr.v[j][i] = row<float>(R, i < M ? i : 0, col);
+    }
+}
+template <int KPL, class RS>
+__device__ __forceinline__ void load_rows(NoRows&, const RS&, int, int, int)
+{
 }
 
 // The knots of a lane (oracle scan_backward_as / scan_forward_as / riccati_sweep_as):
@@ -1090,11 +1123,12 @@ __device__ __forceinline__ void as_pass_h(AKnotT<T>& K, const PT<T>& P, const RS
 // The certificate of one knot after the step (IPM kernel polish block): stationarity with the
 // solve's costates, multiplier signs, primal feasibility of every facet; drop / add bookkeeping.
 // One quotient per knot (c = 1: (a g) / |a|^2; c = 2: 1 / det), operands selected by the case.
-template <class T, class RS>
+// rr, j: the knot's rows in registers (slot j of RegRows), or NoRows: read from LDS.
+template <class T, class RS, class RR>
 __device__ __forceinline__ void as_certify(AKnotT<T>& K, const PT<T>& P, const RS& R, int col, int pk,
                                            T dx0, T dx1, T vn0, T vn1, T& l1o, T& l2o, bool& okp, bool& neg,
                                            bool& viol, bool bland, int& ndrop, int& nadd, const Row<T>& na,
-                                           const Row<T>& ne)
+                                           const Row<T>& ne, const RR& rr, int j)
 {
     const int cx = opaque(col);
     const int pc = pk & 3, pi1 = (pk >> 2) & 15, pi2 = (pk >> 6) & 15;
@@ -1144,8 +1178,12 @@ __device__ __forceinline__ void as_certify(AKnotT<T>& K, const PT<T>& P, const R
         Row<T> rv[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int i = i0 + q < km ? i0 + q : 0;
-            rv[q] = row<T>(R, i, cx);
+            if constexpr (kHasRows<RR>) {   // (rows i >= m fail or pass the test freely: vm is masked below)
+                rv[q] = rr.v[j][i0 + q];
+            } else {
+                const int i = i0 + q < km ? i0 + q : 0;
+                rv[q] = row<T>(R, i, cx);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -1239,22 +1277,34 @@ __device__ __forceinline__ void as_refine(AKnot (&K)[KPL], const PT<double>& P, 
 // violates; the fp64 passes after the fp32 search: kGuessSlack, the facets active at the float
 // point); warm starts add those whose previous multiplier exceeds the floor (lw = that knot's
 // previous multipliers, or nullptr).
-template <int KPL, class T, class RS>
+template <int KPL, class T, class RS, class RR>
 __device__ __forceinline__ void as_guess(AKnotT<T> (&K)[KPL], const RS& R, int NH, int N, int lane,
-                                         const double* const (&lw)[KPL], double ws_floor, T thr)
+                                         const double* const (&lw)[KPL], double ws_floor, T thr, const RR& rr)
 {
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
         const int k = KPL * lane + j;
         if (k < N) {
-            const int col = R.col(j, lane);
             int gm = 0;
-            for (int i = 0; i < K[j].m; ++i) {
-                const Row<T> a = row<T>(R, i, col);
-                const T gr = FD2(a.x, K[j].r0, a.y, K[j].r1);
-                const T sl = a.b - gr;
-                if (sl < thr) gm |= 1 << i;
-                if (lw[j] && lw[j][i] > ws_floor) gm |= 1 << i;
+            if constexpr (kHasRows<RR>) {
+                // the rows in registers (cold starts only: no previous multipliers, lw is null):
+                // every slot, masked by the count
+#pragma unroll
+                for (int i = 0; i < kMaxFacets; ++i) {
+                    const Row<T> a = rr.v[j][i];
+                    const T gr = FD2(a.x, K[j].r0, a.y, K[j].r1);
+                    const T sl = a.b - gr;
+                    if (i < K[j].m && sl < thr) gm |= 1 << i;
+                }
+            } else {
+                const int col = R.col(j, lane);
+                for (int i = 0; i < K[j].m; ++i) {
+                    const Row<T> a = row<T>(R, i, col);
+                    const T gr = FD2(a.x, K[j].r0, a.y, K[j].r1);
+                    const T sl = a.b - gr;
+                    if (sl < thr) gm |= 1 << i;
+                    if (lw[j] && lw[j][i] > ws_floor) gm |= 1 << i;
+                }
             }
             K[j].gm = gm;
         }
@@ -1277,10 +1327,12 @@ __device__ __forceinline__ int as_cand(const AKnotT<T>& K)
 // `handover` knots ends the search, its next candidate sets going to the fp64 passes instead of
 // another float pass (oracle passes32): the last float pass before the
 // certifying one changes a few knots, and the fp64 passes certify that set.  -1: never.
-template <int KPL, int TR, class T, class RS>
+// rr: the rows in registers for the certificate's feasibility scan (RegRows, float), or NoRows.
+template <int KPL, int TR, class T, class RS, class RR>
 __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, const RS& R, int NH, int N,
                                           int lane, T xi00, T xi01, int (&pk)[KPL],
-                                          T (&pl)[KPL][2], int count_slot, int sb, int handover, int& npass)
+                                          T (&pl)[KPL][2], int count_slot, int sb, int handover, int& npass,
+                                          const RR& rr)
 {
     T xk[KPL][2];
     as_xi_prev<KPL, T>(K, lane, xi00, xi01, xk);
@@ -1350,7 +1402,7 @@ __device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, c
                     K[j].x1 = K[j].x1 + dx[j][1];
                     if constexpr (sizeof(T) == 8) as_project<T>(K[j], R, R.col(j, lane), opaque(pk[j]));
                     as_certify<T>(K[j], P, R, R.col(j, lane), opaque(pk[j]), dx[j][0], dx[j][1], vn[j][0], vn[j][1],
-                                  pl[j][0], pl[j][1], okp, neg, viol, kAnti && bland, ndr[j], nad[j], na[j], ne[j]);
+                                  pl[j][0], pl[j][1], okp, neg, viol, kAnti && bland, ndr[j], nad[j], na[j], ne[j], rr, j);
                 }
             }
             AS_STAMP_ADD(sb + 4, t_c);
@@ -1820,13 +1872,18 @@ __device__ __forceinline__ void cold_solve(
         AS_STAMP_ADD(2, t_q);
         AS_STAMP(t_g);
         const double* const lw0[KPL] = {};
-        as_guess<KPL, float>(F, R, NH, N, lane, lw0, 0.0, 0.0f);
+        // the search's rows: read and rounded once, every read issued before the first wait.
+        // Not for the phase-indexed input: its Kogge-Stone warm instances (N = 127, 128) spill
+        // with the rows in registers.
+        std::conditional_t<MF == kMaxFacets && !PH, RegRows<KPL>, NoRows> rr;
+        load_rows<KPL>(rr, R, N, M, lane);
+        as_guess<KPL, float>(F, R, NH, N, lane, lw0, 0.0, 0.0f, rr);
         AS_STAMP_ADD(3, t_g);
         AS_STAMP(t_a);
         int pkf[KPL];
         float plf[KPL][2];
         cert32 = as_passes<KPL, TR, float>(F, Pf, R, NH, N, lane, xf00, xf01, pkf, plf, 12, 16, N / kHandoverDiv,
-                                           npass32);
+                                           npass32, rr);
         AS_STAMP_ADD(13, t_a);
     }
 #pragma unroll
@@ -1888,13 +1945,13 @@ __device__ __forceinline__ void cold_solve(
         const double* const lw0[KPL] = {};
         // (cert32 comes from a ballot: wave-uniform, so the uncertified hand-over skips the rows' reads)
         if (cert32) {
-            as_guess<KPL, double>(K, R, NH, N, lane, lw0, 0.0, kGuessSlack);
+            as_guess<KPL, double>(K, R, NH, N, lane, lw0, 0.0, kGuessSlack, NoRows{});
         } else {
 #pragma unroll
             for (int j = 0; j < KPL; ++j) K[j].gm = KPL * lane + j < N ? cand[j] : 0;
         }
         int npass64 = 0;
-        certified = as_passes<KPL, TR, double>(K, Pd, R, NH, N, lane, xi00, xi01, pk, pl, 10, 4, -1, npass64);
+        certified = as_passes<KPL, TR, double>(K, Pd, R, NH, N, lane, xi00, xi01, pk, pl, 10, 4, -1, npass64, NoRows{});
         npass += npass64;
         if (!certified) {
             // ---- the IPM's start point: the fp64 LQ optimum from (xi_ref, vrp_ref) ----
@@ -2111,10 +2168,10 @@ __global__ __launch_bounds__(kWave, kAsMinWaves) void dcm_mpc_warm_kernel(
             const int k = KPL * lane + j;
             lw[j] = (k < N && k + P.ws_shift < N) ? ws_lam + (p * N + k + P.ws_shift) * M : nullptr;
         }
-        as_guess<KPL, double>(K, R, NH, N, lane, lw, P.ws_floor, 0.0);
+        as_guess<KPL, double>(K, R, NH, N, lane, lw, P.ws_floor, 0.0, NoRows{});
         AS_STAMP_ADD(3, t_g);
         AS_STAMP(t_b);
-        certified = as_passes<KPL, TR, double>(K, Pd, R, NH, N, lane, xi00, xi01, pk, pl, 10, 4, -1, npass);
+        certified = as_passes<KPL, TR, double>(K, Pd, R, NH, N, lane, xi00, xi01, pk, pl, 10, 4, -1, npass, NoRows{});
         AS_STAMP_ADD(14, t_b);
     }
     // the warm passes did not certify: the QP is solved again from a cold start (fp32 search,
@@ -2187,7 +2244,10 @@ blf_status launch_kpl(const KParams& kp, const blf_dcm_mpc_problem* pb, const bl
     constexpr int kAltTree = KPL == 2 ? kTreePad : kTreeDpp;   // the instantiated trees: this, kTreeKS
     const int tr = (KPL == 1 && batch <= kDppTreeMaxBatch) ? kTreeDpp
                    : (KPL == 2 && kp.N <= 2 * kWave - 2) ? kTreePad : kTreeKS;
-    if (KPL == 1 && MF == kMaxFacets && warm == nullptr && ps == nullptr && batch <= kFusedMaxBatch &&
+    // (if constexpr: the fused kernel belongs to this one launcher, so it is instantiated once,
+    // in the object that holds the one-knot-per-lane instances)
+    if constexpr (KPL == 1 && MF == kMaxFacets)
+    if (warm == nullptr && ps == nullptr && batch <= kFusedMaxBatch &&
         qp_launch_mode().fuse_stage2.load(std::memory_order_relaxed)) {
         const size_t lds_f = std::max(lds, sizeof(double) * Lds(nullptr, kp.N, kp.M, 1).total);
         auto kern = lam_out ? dcm_mpc_cold_fused_kernel<true> : dcm_mpc_cold_fused_kernel<false>;
@@ -2241,6 +2301,32 @@ extern "C" int blf_debug_as_stamps(unsigned long long* out, int reset)
 }
 #endif
 
+// The library builds this file as two objects (Makefile), because one compiler option pays for
+// one group of instances and costs the other:
+//   BLF_AS_PART == 2: the knot-pair kernels with 8 facet slots (65 <= N <= 128, the headline
+//       batch's) alone, without SLP vectorisation: at two waves per SIMD they are bound by the
+//       SIMD's issue cycles, where a packed fp32 operation costs two scalar ones and its operand
+//       pair costs moves;
+//   BLF_AS_PART == 1: launch_dcm_mpc_as and every other instance, vectorised as the compiler
+//       likes: a single solve (the fused kernel, one wavefront alone on its SIMD) is bound by its
+//       instruction count, where a packed operation is one issue slot for two results.
+// Undefined: the whole file in one object (the diagnostic builds).
+blf_status launch_as_pairs8(const qp::KParams& kp, const blf_dcm_mpc_problem* pb,
+                            const blf_dcm_mpc_warm_start* warm, int64_t batch,
+                            const blf_dcm_mpc_solution* sol, double* lam_out, hipStream_t s,
+                            const qp::PhaseSrc* ps, bool* stage2_done);
+
+#if !defined(BLF_AS_PART) || BLF_AS_PART == 2
+blf_status launch_as_pairs8(const qp::KParams& kp, const blf_dcm_mpc_problem* pb,
+                            const blf_dcm_mpc_warm_start* warm, int64_t batch,
+                            const blf_dcm_mpc_solution* sol, double* lam_out, hipStream_t s,
+                            const qp::PhaseSrc* ps, bool* stage2_done)
+{
+    return launch_kpl<2, kMaxFacets>(kp, pb, warm, batch, sol, lam_out, s, ps, stage2_done);
+}
+#endif
+
+#if !defined(BLF_AS_PART) || BLF_AS_PART == 1
 // Active-set kernel of a launch_dcm_mpc call (N <= 128, tol_polish > 0): every QP either solved
 // (status 0, polished) or marked kPending for the IPM kernel's stage 2.
 blf_status launch_dcm_mpc_as(const qp::KParams& kp, const blf_dcm_mpc_problem* pb,
@@ -2254,7 +2340,7 @@ blf_status launch_dcm_mpc_as(const qp::KParams& kp, const blf_dcm_mpc_problem* p
     // facet slots: 8, or 16 for phases of three or four contacts (twice the LDS per QP)
     if (kp.M <= kMaxFacets) {
         if (kp.N <= kWave) return launch_kpl<1, kMaxFacets>(kp, pb, warm, batch, sol, lam_out, s, ps, done);
-        if (kp.N <= 2 * kWave) return launch_kpl<2, kMaxFacets>(kp, pb, warm, batch, sol, lam_out, s, ps, done);
+        if (kp.N <= 2 * kWave) return launch_as_pairs8(kp, pb, warm, batch, sol, lam_out, s, ps, done);
     } else if (kp.M <= kMaxFacetsWide) {
         if (kp.N <= kWave) return launch_kpl<1, kMaxFacetsWide>(kp, pb, warm, batch, sol, lam_out, s, ps, done);
         if (kp.N <= 2 * kWave) return launch_kpl<2, kMaxFacetsWide>(kp, pb, warm, batch, sol, lam_out, s, ps, done);
@@ -2263,5 +2349,6 @@ blf_status launch_dcm_mpc_as(const qp::KParams& kp, const blf_dcm_mpc_problem* p
     }
     return set_error(BLF_ERR_UNSUPPORTED, "active-set kernel: horizon %d > 128", kp.N);
 }
+#endif
 
 }  // namespace blf
