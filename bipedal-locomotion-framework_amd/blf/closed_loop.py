@@ -41,6 +41,14 @@ replaces step 3 by the whole-body IK and tracks its trajectory slice by slice:
                      with qd_ref the joint rates of nu_traj.
 blf_fb_ik_track checks its shared weights through a staged copy and waits for it, so in this mode
 period() synchronises with the stream once per period.
+
+ClosedLoop(reference="ik", control="computed_torque") (opt-in; control="impedance" is every mode above,
+launch for launch) replaces step 4 by blf_fbd_euler_integrate_computed_torque_traj over the same slices:
+before every integration step the torque is the free-base inverse dynamics of
+  sdd = kp (q_ref - q) + kd (qd_ref - qdot),   kp = f^2, kd = 2 zeta f   (f = 20, zeta = 1: the
+acceleration gains robot.posture_law_arrays(freq=20) scales by inertia), optionally clamped to tau_max,
+with the feet's contact wrenches and gravity fed forward, so every joint follows its reference by its
+own two-state linear recurrence.  The lean term is off by default in this mode.
 """
 import math
 
@@ -106,17 +114,33 @@ class ClosedLoop:
     their null poses) and robot.humanoid24_joint_limits (sampling time dt / steps); steps IK slices per
     period; lean adds the posture law's ankle lean term as the impedance's bias.  After a period
     ik_status, ik_fail_step, ik_iters [B] and ik_active [B,2] hold blf_fb_ik_track's outputs,
-    joint_traj / nu_traj its trajectory and c_ref the CoM reference's end point."""
+    joint_traj / nu_traj its trajectory and c_ref the CoM reference's end point.
+
+    control="computed_torque" (with reference="ik" only): the period's dynamics call is
+    blf_fbd_euler_integrate_computed_torque_traj, computed_torque=dict(freq=20.0, zeta=1.0, tau_max=None)
+    (kp = freq^2, kd = 2 zeta freq; tau_max a scalar or [n]); ik["lean"] defaults to False; tau_last [B,n]
+    holds the last step's applied torque."""
 
     def __init__(self, h, model, plan, states, horizon=100, dT=0.001, law=None,
                  contact_params=CONTACT_PARAMS, tol_polish=1e-4, stream=None, max_iter=MAX_ITER,
-                 cold_after_handover=None, reference="posture", ik=None):
+                 cold_after_handover=None, reference="posture", ik=None, control="impedance",
+                 computed_torque=None):
         import torch
         if reference not in ("posture", "ik"):
             raise ValueError(f"reference={reference!r}: 'posture' or 'ik'")
         if ik is not None and reference != "ik":
             raise ValueError("ik= goes with reference='ik'")
-        self.reference = reference
+        if control not in ("impedance", "computed_torque"):
+            raise ValueError(f"control={control!r}: 'impedance' or 'computed_torque'")
+        if control == "computed_torque" and reference != "ik":
+            raise ValueError("control='computed_torque' goes with reference='ik'")
+        if computed_torque is not None and control != "computed_torque":
+            raise ValueError("computed_torque= goes with control='computed_torque'")
+        unknown = set(computed_torque or {}) - {"freq", "zeta", "tau_max"}
+        if unknown:
+            raise ValueError(f"computed_torque: unknown entries {sorted(unknown)}")
+        self.reference, self.control = reference, control
+        self._ctq = dict(computed_torque or {})
         self.h, self.N, self.dT, self.stream = h, horizon, dT, stream
         dev = torch.device("cuda", h.device)
         t = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
@@ -195,13 +219,19 @@ class ClosedLoop:
         i32 = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)
         self.ik_status, self.ik_fail_step, self.ik_iters = i32(B), i32(B), i32(B)
         self.ik_active = torch.zeros((B, 2), dtype=torch.int64, device=dev)
-        self.lean = bool(ik.get("lean", True))
+        self.lean = bool(ik.get("lean", self.control != "computed_torque"))
         self.q_bias = f64(B, n) if self.lean else None
         if self.lean:   # the ankle lean term alone: the posture law about q_nominal = 0
             self.lean_law = h.posture_law(np.zeros(n), law["lean"])
         self.steps_per_slice = -(-len(self.steps) // T)
         self.traj = h.joint_impedance_traj(self.imp, self.joint_traj, self.steps_per_slice, qd_ref=self.nu_traj,
                                            qd_offset=6, q_bias=self.q_bias)
+        if self.control == "computed_torque":   # the same slices under the computed-torque law
+            f, zeta = float(self._ctq.get("freq", 20.0)), float(self._ctq.get("zeta", 1.0))
+            self.tau_last = f64(B, n)
+            self.ctq = h.computed_torque_traj(f * f, 2.0 * zeta * f, self.joint_traj, self.steps_per_slice,
+                                              qd_ref=self.nu_traj, qd_offset=6, q_bias=self.q_bias,
+                                              tau_max=self._ctq.get("tau_max"), tau_last=self.tau_last)
 
     def _ik_reference(self, out, s):
         """Steps 3 and 4 of the IK period: the plan's CoM schedule, then the IK over it."""
@@ -264,7 +294,10 @@ class ClosedLoop:
             st = self.stream if self.stream is not None else torch.cuda.current_stream()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(st)
-        if self.reference == "ik":   # slice by slice: joint_traj, nu_traj's joint rates, the lean term
+        if self.control == "computed_torque":   # the same slices, the torques from inverse dynamics
+            h.fbd_euler_integrate_computed_torque_traj(self.dm, self.state, self.ctq, 0.0, self.T, self.dT,
+                                                       contacts=self.contacts, stream=self.stream)
+        elif self.reference == "ik":   # slice by slice: joint_traj, nu_traj's joint rates, the lean term
             h.fbd_euler_integrate_impedance_traj(self.dm, self.state, self.traj, 0.0, self.T, self.dT,
                                                  contacts=self.contacts, stream=self.stream)
         else:

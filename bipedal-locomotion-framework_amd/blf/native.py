@@ -33,7 +33,8 @@ EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_s
             "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate",
             "blf_fb_ik_solve_hard", "blf_fb_ik_integrate_hard", "blf_fb_ik_solve_limits",
             "blf_fb_ik_integrate_limits", "blf_fb_ik_track",
-            "blf_fbd_euler_integrate_impedance_traj", "blf_dcm_com_reference"]
+            "blf_fbd_euler_integrate_impedance_traj", "blf_dcm_com_reference",
+            "blf_fb_inverse_dynamics", "blf_fbd_euler_integrate_computed_torque_traj"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -82,6 +83,13 @@ class JointImpedanceTraj(ctypes.Structure):
     _fields_ = [("ndof", _i32), ("slices", _i32), ("steps_per_slice", _i32), ("reserved", _i32),
                 ("kp", _vp), ("kd", _vp), ("q_ref", _vp), ("qd_ref", _vp), ("qd_stride", _i64),
                 ("q_bias", _vp)]
+
+
+class ComputedTorqueTraj(ctypes.Structure):
+    """blf_computed_torque_traj: computed torque from inverse dynamics, references indexed by the step."""
+    _fields_ = [("ndof", _i32), ("slices", _i32), ("steps_per_slice", _i32), ("reserved", _i32),
+                ("kp", _vp), ("kd", _vp), ("q_ref", _vp), ("qd_ref", _vp), ("qd_stride", _i64),
+                ("qdd_ref", _vp), ("qdd_stride", _i64), ("q_bias", _vp), ("tau_max", _vp), ("tau_last", _vp)]
 
 
 class SwingFootParams(ctypes.Structure):
@@ -247,6 +255,11 @@ def lib():
             ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
         L.blf_fbd_euler_integrate_impedance_traj.argtypes = [
             _vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), ctypes.POINTER(JointImpedanceTraj),
+            ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
+        L.blf_fb_inverse_dynamics.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), _vp, _vp,
+                                              ctypes.POINTER(FbContacts), _i64, _vp, _vp, _vp, _vp, _i32, _vp]
+        L.blf_fbd_euler_integrate_computed_torque_traj.argtypes = [
+            _vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), ctypes.POINTER(ComputedTorqueTraj),
             ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
         L.blf_dcm_com_reference.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _i64,
                                             _vp, _vp, _vp, _vp]
@@ -1036,6 +1049,36 @@ class Handle:
                                         _stream(stream)))
         return pose, twist
 
+    def fb_inverse_dynamics(self, dm, state, joint_acc=None, base_acc=None, contacts=None, joint_torque=None,
+                            base_acc_out=None, base_wrench=None, status=None, stream=None):
+        """blf_fb_inverse_dynamics (include/blf/blf_c.h section 8b) at `state` with joint accelerations
+        joint_acc [B,n] (None: zero).  base_acc None: the free-base mode, returns dict(joint_torque [B,n],
+        base_acc [B,6], status [B] int32); base_acc [B,6] given: returns dict(joint_torque, base_wrench
+        [B,6] (force, torque; mixed, at the base origin), status).  status False leaves it out."""
+        torch = _torch()
+        B, n = state["joint_pos"].shape
+        dev = state["joint_pos"].device
+        new = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
+        tau = joint_torque if joint_torque is not None else new((B, n))
+        if status is None:
+            status = torch.empty((B,), dtype=torch.int32, device=dev)
+        given = base_acc is not None
+        if given:
+            six = base_wrench if base_wrench is not None else new((B, 6))
+        else:
+            six = base_acc_out if base_acc_out is not None else new((B, 6))
+        sp = _ptr(six, torch.float64, (B, 6), "base_wrench" if given else "base_acc_out")
+        _check(lib().blf_fb_inverse_dynamics(
+            self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
+            _ptr(joint_acc, torch.float64, (B, n), "joint_acc") if joint_acc is not None else None,
+            _ptr(base_acc, torch.float64, (B, 6), "base_acc") if given else None,
+            ctypes.byref(self._fb_contacts(contacts, B)), B, _ptr(tau, torch.float64, (B, n), "joint_torque"),
+            None if given else sp, sp if given else None,
+            _ptr(status, torch.int32, (B,), "status") if status is not False else None, 0, _stream(stream)))
+        out = dict(joint_torque=tau, status=status if status is not False else None)
+        out["base_wrench" if given else "base_acc"] = six
+        return out
+
     # ---- whole-body inverse kinematics (include/blf/blf_c.h section 12) ------------------------
     def ik_tasks(self, batch, ndof, frame=None, se3_weight=None, se3_kp=None, se3_pose=None, se3_twist=None,
                  com_weight=None, com_kp=0.0, com_pos=None, com_vel=None, joint_weight=None,
@@ -1393,6 +1436,74 @@ class Handle:
         args = (self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(traj.c),
                 ctypes.byref(self._fb_contacts(contacts, B)), reg, B, float(t0), float(t1), float(dT))
         _check(lib().blf_fbd_euler_integrate_impedance_traj(*args, _stream(stream)))
+        return state
+
+    def computed_torque_traj(self, kp, kd, q_ref, steps_per_slice, qd_ref=None, qd_offset=0, qdd_ref=None,
+                             q_bias=None, tau_max=None, qdd_offset=0, tau_last=None):
+        """A blf_computed_torque_traj: acceleration gains kp, kd (scalars or [n]; host values or device
+        tensors), q_ref [T,B,n], qd_ref / qdd_ref [T,B,w] or None with the joint columns at qd_offset /
+        qdd_offset (fb_ik_track's nu_traj with qd_offset = 6), q_bias [B,n] or None, tau_max (scalar or
+        [n], finite and > 0) or None, tau_last [B,n] (True allocates) or None.  Returns an object with the
+        struct (.c) and the tensors (.t) it keeps alive."""
+        torch = _torch()
+
+        class _T:
+            pass
+        it = _T()
+        T, B, n = q_ref.shape
+        dev = q_ref.device
+
+        def vec(a, name):
+            if isinstance(a, torch.Tensor) and a.is_cuda:
+                return a
+            v = torch.as_tensor(a, dtype=torch.float64).reshape(-1)
+            return (v.expand(n) if v.numel() == 1 else v).contiguous().to(dev)
+        c = ComputedTorqueTraj()
+        c.ndof, c.slices, c.steps_per_slice, c.reserved = n, T, int(steps_per_slice), 0
+        it.t = dict(kp=vec(kp, "kp"), kd=vec(kd, "kd"), q_ref=q_ref, qd_ref=qd_ref, qdd_ref=qdd_ref, q_bias=q_bias)
+        c.kp = _ptr(it.t["kp"], torch.float64, (n,), "kp")
+        c.kd = _ptr(it.t["kd"], torch.float64, (n,), "kd")
+        c.q_ref = _ptr(q_ref, torch.float64, (T, B, n), "q_ref")
+        for name, ref, off in (("qd", qd_ref, qd_offset), ("qdd", qdd_ref, qdd_offset)):
+            if ref is None:
+                continue
+            w = ref.shape[-1]
+            _ptr(ref, torch.float64, (T, B, w), name + "_ref")
+            if not 0 <= off <= w - n:
+                raise ValueError(f"{name}_ref: columns {off}..{off + n} outside [0, {w})")
+            setattr(c, name + "_ref", _vp(ref.data_ptr() + 8 * int(off)))
+            setattr(c, name + "_stride", w)
+        if q_bias is not None:
+            c.q_bias = _ptr(q_bias, torch.float64, (B, n), "q_bias")
+        if tau_max is not None:
+            if not (isinstance(tau_max, torch.Tensor) and tau_max.is_cuda):   # host values: checked here
+                tm = torch.as_tensor(tau_max, dtype=torch.float64)
+                if not bool((torch.isfinite(tm) & (tm > 0)).all()):
+                    raise ValueError("tau_max: every entry must be finite and > 0")
+            it.t["tau_max"] = vec(tau_max, "tau_max")
+            c.tau_max = _ptr(it.t["tau_max"], torch.float64, (n,), "tau_max")
+        if tau_last is True:
+            tau_last = torch.empty((B, n), dtype=torch.float64, device=dev)
+        if tau_last is not None:
+            c.tau_last = _ptr(tau_last, torch.float64, (B, n), "tau_last")
+        it.t["tau_last"] = it.tau_last = tau_last
+        it.c, it.batch = c, B
+        return it
+
+    def fbd_euler_integrate_computed_torque_traj(self, dm, state, law, t0, t1, dT, contacts=None, mass_reg=None,
+                                                 stream=None):
+        """blf_fbd_euler_integrate_computed_torque_traj in place on `state`: before every step the torque
+        is the free-base inverse dynamics of sdd = qdd_ref + kp (q_ref + q_bias - q) + kd (qd_ref - qdot),
+        clamped to tau_max, then the forward step (law: computed_torque_traj()).  mass_reg is refused."""
+        torch = _torch()
+        B, n = state["joint_pos"].shape
+        NV = n + 6
+        if law.batch != B:
+            raise ValueError(f"the trajectory holds {law.batch} robots, the state {B}")
+        reg = _ptr(mass_reg, torch.float64, (NV, NV), "mass_reg") if mass_reg is not None else None
+        args = (self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(law.c),
+                ctypes.byref(self._fb_contacts(contacts, B)), reg, B, float(t0), float(t1), float(dT))
+        _check(lib().blf_fbd_euler_integrate_computed_torque_traj(*args, _stream(stream)))
         return state
 
     def dcm_com_reference(self, xi0, vrp, omega, z_ref, c_ref, steps, dT, column=0, com_pos=None, com_vel=None,

@@ -835,6 +835,89 @@ blf_status blf_fbd_euler_integrate_impedance_traj(blf_handle* handle, const blf_
                                  (hipStream_t)stream, impedance);
 }
 
+}  // extern "C"
+
+// The checks of section 8b and the computed-torque call: invalid arguments first, then the sizes
+// the kernels are not built for (BLF_ERR_UNSUPPORTED, as the whole-body IK calls report them).
+static blf_status check_invdyn(const char* fn, blf_handle* handle, const blf_fb_model* model,
+                               const blf_fb_state* state, const blf_fb_contacts* contacts, int64_t batch)
+{
+    BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
+    BLF_REQUIRE(model != nullptr && state != nullptr, "%s: null model / state", fn);
+    BLF_REQUIRE(batch >= 0, "%s: negative batch", fn);
+    BLF_REQUIRE(model->parent && model->joint_origin && model->joint_rot && model->joint_axis &&
+                    model->link_mass && model->link_com && model->link_inertia,
+                "%s: null model array", fn);
+    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel && state->base_pos && state->base_rot &&
+                               state->joint_pos),
+                "%s: null state buffer", fn);
+    const int C = contacts ? contacts->ncontacts : 0;
+    BLF_REQUIRE(C >= 0, "%s: %d contacts", fn, C);
+    if (model->ndof < 1 || model->ndof > BLF_FBD_MAX_DOFS)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: ndof=%d outside [1, %d]", fn, model->ndof, BLF_FBD_MAX_DOFS);
+    if (C > BLF_FBD_MAX_CONTACTS)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: %d contacts, at most %d", fn, C, BLF_FBD_MAX_CONTACTS);
+    BLF_REQUIRE(C == 0 || (contacts->frame && contacts->params && contacts->null_pose &&
+                           model->frame_link && model->frame_pose && model->nframes > 0),
+                "%s: null contact buffer", fn);
+    BLF_REQUIRE(C == 0 || contacts->law == nullptr || batch == 0 || contacts->wrench != nullptr,
+                "%s: contact laws given without the wrench buffer", fn);
+    if (fbd_lds_bytes(model->ndof, C, true) > 160 * 1024 / 2)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    return BLF_OK;
+}
+
+extern "C" {
+
+blf_status blf_fb_inverse_dynamics(blf_handle* handle, const blf_fb_model* model,
+                                   const blf_fb_state* state, const double* joint_acc,
+                                   const double* base_acc, const blf_fb_contacts* contacts,
+                                   int64_t batch, double* joint_torque, double* base_acc_out,
+                                   double* base_wrench, int32_t* status, int32_t reserved,
+                                   void* stream)
+{
+    const char* fn = "blf_fb_inverse_dynamics";
+    BLF_REQUIRE(reserved == 0, "%s: reserved must be 0", fn);
+    blf_status st = check_invdyn(fn, handle, model, state, contacts, batch);
+    if (st != BLF_OK) return st;
+    double* const bout = base_acc ? base_wrench : base_acc_out;
+    BLF_REQUIRE(batch == 0 || (joint_torque && bout), "%s: null %s", fn,
+                !joint_torque ? "joint_torque" : base_acc ? "base_wrench (given-base mode)" : "base_acc_out (free-base mode)");
+    return launch_fb_invdyn(model, state, joint_acc, base_acc, contacts, batch, joint_torque, bout, status,
+                            (hipStream_t)stream);
+}
+
+blf_status blf_fbd_euler_integrate_computed_torque_traj(blf_handle* handle, const blf_fb_model* model,
+                                                        const blf_fb_state* state,
+                                                        const blf_computed_torque_traj* law,
+                                                        const blf_fb_contacts* contacts,
+                                                        const double* mass_reg, int64_t batch,
+                                                        double initial_time, double final_time,
+                                                        double dT, void* stream)
+{
+    const char* fn = "blf_fbd_euler_integrate_computed_torque_traj";
+    BLF_REQUIRE(law != nullptr, "%s: null law", fn);
+    BLF_REQUIRE(law->reserved == 0, "%s: reserved must be 0", fn);
+    BLF_REQUIRE(law->slices >= 1 && law->steps_per_slice >= 1, "%s: slices=%d, steps_per_slice=%d, both must be >= 1",
+                fn, law->slices, law->steps_per_slice);
+    BLF_REQUIRE(law->kp && law->kd && (batch == 0 || law->q_ref), "%s: null law array", fn);
+    BLF_REQUIRE(model != nullptr && law->ndof == model->ndof, "%s: law ndof %d != model ndof %d", fn, law->ndof,
+                model ? model->ndof : -1);
+    BLF_REQUIRE(law->qd_ref == nullptr || law->qd_stride >= law->ndof, "%s: qd_stride=%lld below ndof=%d", fn,
+                (long long)law->qd_stride, law->ndof);
+    BLF_REQUIRE(law->qdd_ref == nullptr || law->qdd_stride >= law->ndof, "%s: qdd_stride=%lld below ndof=%d", fn,
+                (long long)law->qdd_stride, law->ndof);
+    blf_status st = check_invdyn(fn, handle, model, state, contacts, batch);
+    if (st != BLF_OK) return st;
+    if (mass_reg != nullptr)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: mass_reg given (inverse dynamics is defined without it)", fn);
+    int iterations = 0;
+    double dT_last = 0.0;
+    st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
+    if (st != BLF_OK) return st;
+    return launch_fbd_euler_ctq(model, state, contacts, batch, iterations, dT, dT_last, (hipStream_t)stream, law);
+}
+
 blf_status blf_dcm_com_reference(blf_handle* handle, const double* xi0, const double* vrp,
                                  int64_t vrp_stride, const double* omega0, int64_t omega0_stride,
                                  const double* z_ref, double* c_ref, int32_t steps, double dT,

@@ -140,6 +140,13 @@ blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, cons
 blf_status launch_fbd_euler_traj(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
                                  const double* reg, int64_t batch, int32_t nsteps, double dT, double dT_last,
                                  hipStream_t s, const blf_joint_impedance_traj* impedance);
+// base_acc == nullptr: the free-base mode (bout = base_acc_out), otherwise bout = base_wrench
+blf_status launch_fb_invdyn(const blf_fb_model* md, const blf_fb_state* st, const double* joint_acc,
+                            const double* base_acc, const blf_fb_contacts* ct, int64_t batch, double* tau,
+                            double* bout, int32_t* status, hipStream_t s);
+blf_status launch_fbd_euler_ctq(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
+                                int64_t batch, int32_t nsteps, double dT, double dT_last, hipStream_t s,
+                                const blf_computed_torque_traj* law);
 blf_status launch_com_reference(const double* xi0, const double* vrp, int64_t vstride, const double* omega0,
                                 int64_t ostride, const double* zref, double* cref, int32_t T, double dT,
                                 int64_t batch, double* cpos, double* cvel, double* xiend, hipStream_t s);

@@ -41,6 +41,9 @@
 //   columns per step, lane per row, the pivot columns through LDS behind a wavefront fence (no
 //   s_barrier);  9. forward and back substitution with the right-hand side in registers (lane per
 //   row, the unknowns broadcast by v_readlane).
+// The inverse dynamics (fbd_id_eval: blf_fb_inverse_dynamics and the computed-torque Euler kernel)
+// shares steps 1, 4 and 3 and replaces the solve by one outward and one inward pass (its own header
+// below).
 #include "blf_internal.h"
 #include "contact_math.h"
 #include "dcm_qp_common.h"   // the DPP prefix-scan levels (qp::tree_fwd / tree_has)
@@ -1088,6 +1091,476 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_traj_kernel(Mo
     }
 }
 
+// ---- Inverse dynamics (blf_fb_inverse_dynamics, blf_c.h section 8b): the hybrid form, joint
+//      accelerations prescribed and the base either free or prescribed.  In the reference-point
+//      formulation of fbd_eval / fbd_aba no transform separates a link from its parent, so with
+//      s_j joint j's motion axis about the point, I_l / F_l step 3's spatial inertia and nu_dot = 0
+//      force (contacts subtracted) and da_0 the base's spatial acceleration relative to nu_dot = 0:
+//        a'_l = sum_{j in anc(l)} s_j sdd_j          (a plain sum over the ancestor mask)
+//        f_l  = F_l + I_l a'_l,   I_tot = sum_l I_l,   p_tot = sum_l f_l
+//        free base:  I_tot da_0 = -p_tot              (the 6 x 6 LDL^T of fbd_aba's base step)
+//        given base: da_0 = S_B nu_dot_B,  base wrench = S_B^T (p_tot + I_tot da_0)
+//        tau_j = s_j^T sum_{l : j in anc(l)} (f_l + I_l da_0).
+//      One sweep out, two wave sums and one sweep in: no level-by-level articulated sweep and no
+//      (n + 6)^2 factorization.  The subtree sum of tau_j is taken by every joint lane over the
+//      links' ancestor masks (n broadcast reads of 6 doubles, no wave sync per tree level and no
+//      prefix differences, whatever the joint order).
+// A link record's doubles 16..21 in the articulated-body layout: free once step 3 has run; they
+// hold s_j sdd_j (joint j in link j + 1's record) and then f_l + I_l da_0 (link l's).
+constexpr int kIDa = 16;
+
+// (m, h, Ibar) times the motion vector (w; u): (Ibar w + h x u; w x h + m u)
+__device__ __forceinline__ void spatial_mv(const double* I, const double* x, double* y)
+{
+    double Iw[3], hu[3], wh[3];
+    sym_mv(I + 4, x, Iw);
+    cross3(I + 1, x + 3, hu);
+    cross3(x, I + 1, wh);
+    for (int a = 0; a < 3; ++a) {
+        y[a] = Iw[a] + hu[a];
+        y[3 + a] = wh[a] + I[0] * x[3 + a];
+    }
+}
+
+// The sum of v over the system's half of the wavefront, in every lane of it (a butterfly: the
+// same bits in every lane).
+template <int HW>
+__device__ __forceinline__ double half_sum(double v)
+{
+#pragma unroll
+    for (int off = HW / 2; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, kWave);
+    return v;
+}
+
+// One inverse-dynamics evaluation for the system whose state sits in LDS.  sdd (LDS, [n]): the
+// joint accelerations on entry, the joint torques on return.  given: bacc is nu_dot_B (mixed) and
+// bout receives the base wrench (force, torque; mixed, at the base origin); otherwise bout
+// receives nu_dot_B.  Every lane returns the same bout.  Returns false if a pivot of I_tot was not
+// a finite positive number.  Steps 1, 4 and 3 are fbd_eval's, as text of their own in the
+// articulated-body layout (that function's instantiations keep their assembly).
+template <int HW, bool PRI, bool CS>
+__device__ __forceinline__ bool fbd_id_eval(const Model& m, const Smem& S, const double* bv, const double* jvel,
+                                            const double* bp, const double* bR, const double* jp, double* sdd,
+                                            const bool given, const double (&bacc)[6], double (&bout)[6],
+                                            const Contacts& ct, int64_t sys, const Topo& T, const double* ref)
+{
+    const Half<HW> H;
+    const int n = m.n, L = n + 1;
+    const int lane = H.hl;
+    const bool jl = lane < n;
+    fbd_kinematics<HW, PRI>(m, S, bv, jvel, bp, bR, jp, T);
+    // 4. contacts (fbd_eval's step 4)
+    for (int c = lane; c < ct.C; c += HW) {
+        int l;
+        const double* fp;
+        if constexpr (CS) {
+            l = (int)S.cst()[c];
+            fp = S.cst() + ct.C + 12 * c;
+        } else {
+            const int f = ct.frame[c];
+            l = m.flink[f];
+            fp = m.fpose + 12 * f;
+        }
+        double pose[12], tw[6];
+        frame_state(S.link() + S.lrec * l, fp, pose, tw);
+        double* sc = S.cscr() + kCs * c;
+        if (given_wrench(ct, c)) {
+            const double* gw = ct.wrench + (sys * ct.C + c) * 6;
+            for (int a = 0; a < 6; ++a) sc[3 + a] = gw[a];
+        } else if constexpr (CS)
+            contact_wrench(S.cst() + 25 * ct.C + 4 * c, tw, pose, S.cst() + 13 * ct.C + 12 * c, sc + 3);
+        else {
+            const double* np = ct.null_pose + (sys * ct.C + c) * 12;
+            double ns[12];   // the null pose relative to the reference point
+            for (int a = 0; a < 12; ++a) ns[a] = a < 3 ? np[a] - ref[a] : np[a];
+            contact_wrench(ct.params + 4 * c, tw, pose, ns, sc + 3);
+        }
+        sc[0] = pose[0]; sc[1] = pose[1]; sc[2] = pose[2];
+        sc[9] = (double)l;
+        double xf[3];
+        cross3(sc, sc + 3, xf);
+        for (int a = 0; a < 3; ++a) {
+            sc[10 + a] = sc[6 + a] + xf[a];
+            sc[13 + a] = sc[3 + a];
+        }
+    }
+    wave_sync();
+    // 3. per link: the spatial inertia and the nu_dot = 0 force about the reference point, contacts
+    //    subtracted (fbd_eval's step 3), over the record's kinematics
+    for (int l = lane; l < L; l += HW) {
+        double* k = S.link() + S.lrec * l;
+        const double* R = k + kR;
+        const double* cl = m.com + 3 * l;
+        const double* Ic = m.inertia + 9 * l;
+        double rc[3], c[3];
+        for (int a = 0; a < 3; ++a) {
+            rc[a] = (R[3 * a] * cl[0] + R[3 * a + 1] * cl[1]) + R[3 * a + 2] * cl[2];
+            c[a] = k[kP + a] + rc[a];
+        }
+        double RI[9];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b)
+                RI[3 * a + b] = (R[3 * a] * Ic[b] + R[3 * a + 1] * Ic[3 + b]) + R[3 * a + 2] * Ic[6 + b];
+        const int ii[6] = {0, 0, 0, 1, 1, 2}, jj[6] = {0, 1, 2, 1, 2, 2};
+        double Iw[6];
+        for (int e = 0; e < 6; ++e) {
+            const int a = ii[e], b = jj[e];
+            Iw[e] = (RI[3 * a] * R[3 * b] + RI[3 * a + 1] * R[3 * b + 1]) + RI[3 * a + 2] * R[3 * b + 2];
+        }
+        double t1[3], t2[3], t3[3], f[3];
+        cross3(k + kAl, rc, t1);
+        cross3(k + kW, rc, t2);
+        cross3(k + kW, t2, t3);
+        const double ms = m.mass[l];
+        const double g[3] = {m.g0, m.g1, m.g2};
+        for (int a = 0; a < 3; ++a) f[a] = ms * (((k[kA + a] + t1[a]) + t3[a]) - g[a]);
+        double Ia[3], Iwv[3], tq[3], cf[3];
+        sym_mv(Iw, k + kAl, Ia);
+        sym_mv(Iw, k + kW, Iwv);
+        cross3(k + kW, Iwv, t1);
+        for (int a = 0; a < 3; ++a) tq[a] = Ia[a] + t1[a];
+        cross3(c, f, cf);
+        const double cc = dot3(c, c);
+        double sfv[6];
+        for (int a = 0; a < 3; ++a) {
+            sfv[a] = tq[a] + cf[a];
+            sfv[3 + a] = f[a];
+        }
+        for (int cc2 = 0; cc2 < ct.C; ++cc2) {
+            const double* sc = S.cscr() + kCs * cc2;
+            const bool hit = (int)sc[9] == l;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) sfv[a] = hit ? sfv[a] - sc[10 + a] : sfv[a];
+        }
+        double* si = k + kSIa;
+        si[0] = ms;
+        si[1] = ms * c[0]; si[2] = ms * c[1]; si[3] = ms * c[2];
+        si[4] = Iw[0] + ms * (cc - c[0] * c[0]);
+        si[5] = Iw[1] - ms * (c[0] * c[1]);
+        si[6] = Iw[2] - ms * (c[0] * c[2]);
+        si[7] = Iw[3] + ms * (cc - c[1] * c[1]);
+        si[8] = Iw[4] - ms * (c[1] * c[2]);
+        si[9] = Iw[5] + ms * (cc - c[2] * c[2]);
+        double* sf = k + kSFa;
+        for (int a = 0; a < 6; ++a) sf[a] = sfv[a];
+    }
+    wave_sync();
+    double* const rec = S.link();
+    const int lr = S.lrec;
+    // joint lane: the motion axis s = (w; u), and s sdd into the joint's child link's record
+    double sv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (jl) {
+        const double* z = S.jz() + 3 * lane;
+        if (PRI && m.jtype[lane] == BLF_JOINT_PRISMATIC) {
+            sv[3] = z[0]; sv[4] = z[1]; sv[5] = z[2];
+        } else {
+            sv[0] = z[0]; sv[1] = z[1]; sv[2] = z[2];
+            cross3(S.jo() + 3 * lane, z, sv + 3);
+        }
+        const double qdd = sdd[lane];
+        double* o = rec + lr * (lane + 1) + kIDa;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) o[a] = sv[a] * qdd;
+    }
+    wave_sync();
+    // link lane: a' over the ancestor joints (base to link), f = F + I a'
+    double I[10], f[6];
+#pragma unroll
+    for (int e = 0; e < 10; ++e) I[e] = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) f[a] = 0.0;
+    if (lane < L) {
+        const double* k = rec + lr * lane;
+#pragma unroll
+        for (int e = 0; e < 10; ++e) I[e] = k[kSIa + e];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) f[a] = k[kSFa + a];
+        double ap[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (unsigned long long b = S.anc()[lane]; b; b &= b - 1) {
+            const double* c = rec + lr * (__builtin_ctzll(b) + 1) + kIDa;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) ap[a] = ap[a] + c[a];
+        }
+        double Ia[6];
+        spatial_mv(I, ap, Ia);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) f[a] = f[a] + Ia[a];
+    }
+    // the whole-body inertia and force (every lane)
+    double It[10], pt[6];
+#pragma unroll
+    for (int e = 0; e < 10; ++e) It[e] = half_sum<HW>(I[e]);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) pt[a] = half_sum<HW>(f[a]);
+    double pB[3] = {bp[0], bp[1], bp[2]};
+    double da[6];
+    bool ok = true;
+    if (given) {   // da_0 = S_B nu_dot_B: w = the angular part, u = the linear part + p_B x w
+        double pw[3];
+        cross3(pB, bacc + 3, pw);
+        for (int a = 0; a < 3; ++a) {
+            da[a] = bacc[3 + a];
+            da[3 + a] = bacc[a] + pw[a];
+        }
+    } else {       // I_tot da_0 = -p_tot: fbd_aba's base step
+        double IA[21];
+        spatial6(It, IA);
+        double Lw[21], d[6], x[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double dj = IA[s6(j, j)];
+#pragma unroll
+            for (int c = 0; c < j; ++c) dj = dj - (Lw[s6(j, c)] * Lw[s6(j, c)]) * d[c];
+            ok = ok && dj > 0.0 && __builtin_isfinite(dj);
+            d[j] = dj;
+            const double idj = 1.0 / dj;
+#pragma unroll
+            for (int i = j + 1; i < 6; ++i) {
+                double t = IA[s6(i, j)];
+#pragma unroll
+                for (int c = 0; c < j; ++c) t = t - (Lw[s6(i, c)] * Lw[s6(j, c)]) * d[c];
+                Lw[s6(i, j)] = t * idj;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double t = -pt[i];
+#pragma unroll
+            for (int c = 0; c < i; ++c) t = t - Lw[s6(i, c)] * x[c];
+            x[i] = t;
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {
+            double t = x[i] / d[i];
+#pragma unroll
+            for (int c = i + 1; c < 6; ++c) t = t - Lw[s6(c, i)] * da[c];
+            da[i] = t;
+        }
+    }
+    if (given) {   // S_B^T (p_tot + I_tot da_0): the force, and the moment taken to the base origin
+        double Id[6], P[6], pf[3];
+        spatial_mv(It, da, Id);
+        for (int a = 0; a < 6; ++a) P[a] = pt[a] + Id[a];
+        cross3(pB, P + 3, pf);
+        for (int a = 0; a < 3; ++a) {
+            bout[a] = P[3 + a];
+            bout[3 + a] = P[a] - pf[a];
+        }
+    } else {       // nu_dot_B from da_0, as at the end of fbd_aba
+        double pw[3];
+        cross3(pB, da, pw);
+        for (int a = 0; a < 3; ++a) {
+            bout[a] = da[3 + a] - pw[a];
+            bout[3 + a] = da[a];
+        }
+    }
+    wave_sync();   // every a' is read
+    if (lane < L) {
+        double Id[6];
+        spatial_mv(I, da, Id);
+        double* o = rec + lr * lane + kIDa;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) o[a] = f[a] + Id[a];
+    }
+    wave_sync();
+    // joint lane: tau = s^T (the sum over the links the joint moves)
+    if (jl) {
+        double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int l = 1; l <= n; ++l) {   // every lane reads the same record: broadcasts
+            const bool hit = (S.anc()[l] >> lane) & 1ull;
+            const double* c = rec + lr * l + kIDa;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) acc[a] = hit ? acc[a] + c[a] : acc[a];
+        }
+        sdd[lane] = dot3(sv, acc) + dot3(sv + 3, acc + 3);
+    }
+    wave_sync();
+    return H.ballot(!ok) == 0ull;
+}
+
+// blf_fb_inverse_dynamics: one system per wavefront, or two while n + 6 <= 32 (fbd_dynamics_kernel's
+// layouts and staging).  bacc == nullptr: the free-base mode, bout = base_acc_out; otherwise the
+// given-base mode, bout = base_wrench.
+template <int HW, bool PRI>
+__global__ __launch_bounds__(64) void fb_invdyn_kernel(Model m, blf_fb_state st, const double* __restrict__ sdd,
+                                                       const double* __restrict__ bacc, Contacts ct,
+                                                       double* __restrict__ tau, double* __restrict__ bout,
+                                                       int32_t* __restrict__ status, int64_t batch)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const Half<HW> H;
+    const int n = m.n;
+    const Smem S(smem + H.half * Smem(nullptr, n, ct.C, true).total, n, ct.C, true);
+    const int64_t q0 = (int64_t)blockIdx.x * (kWave / HW) + H.half;
+    const bool active = q0 < batch;   // see fbd_dynamics_kernel
+    const int64_t q = active ? q0 : batch - 1;
+    const int lane = H.hl;
+    double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n
+    bool fin = true;
+    for (int i = lane; i < 18 + 2 * n; i += HW) {
+        double v;
+        if (i < 6) v = st.base_vel[6 * q + i];
+        else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
+        else if (i < 9 + n) {   // the reference point; the position relative to it starts at zero
+            const double r = st.base_pos[3 * q + (i - 6 - n)];
+            loc[kRef(n) + (i - 6 - n)] = r;
+            fin = fin && __builtin_isfinite(r);
+            v = 0.0;
+        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
+        fin = fin && __builtin_isfinite(v);
+        loc[i] = v;
+    }
+    for (int j = lane; j < n; j += HW) {
+        const double v = sdd ? sdd[(int64_t)n * q + j] : 0.0;
+        fin = fin && __builtin_isfinite(v);
+        S.tq()[j] = v;
+    }
+    double ba[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, bo[6];
+    if (bacc)
+        for (int a = 0; a < 6; ++a) {
+            ba[a] = bacc[6 * q + a];
+            fin = fin && __builtin_isfinite(ba[a]);
+        }
+    for (int c = lane; c < ct.C; c += HW)
+        if (given_wrench(ct, c))
+            for (int a = 0; a < 6; ++a) fin = fin && __builtin_isfinite(ct.wrench[(q * ct.C + c) * 6 + a]);
+    wave_sync();
+    const Topo T = build_topo<HW>(m, S);
+    const bool pos = fbd_id_eval<HW, PRI, false>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n, S.tq(),
+                                                 bacc != nullptr, ba, bo, ct, q, T, loc + kRef(n));
+    if (!active) return;
+    const bool bad = H.ballot(!fin) != 0ull;
+    const bool ok = pos && !bad;
+    const double nan = __builtin_nan("");
+    for (int j = lane; j < n; j += HW) tau[(int64_t)n * q + j] = ok ? S.tq()[j] : nan;
+    if (lane < 6) {
+        // (selects, not a lane-indexed array: that would live in scratch)
+        const double v = lane == 0 ? bo[0] : lane == 1 ? bo[1] : lane == 2 ? bo[2] : lane == 3 ? bo[3] : lane == 4 ? bo[4] : bo[5];
+        bout[6 * q + lane] = ok ? v : nan;
+    }
+    if (status && lane == 0) status[q] = bad ? BLF_IK_BAD_INPUT : pos ? BLF_IK_OK : BLF_IK_NOT_POSITIVE;
+}
+
+// blf_fbd_euler_integrate_computed_torque_traj: fbd_euler_traj_kernel's schedule, slices, step and
+// write-back with the torque law replaced by the inverse dynamics of the commanded acceleration,
+//   sdd = qddref + kp (qref + qbias - q) + kd (qdref - qdot),  tau = clamp(ID(sdd), tau_max),
+// taken at every step's start state (the torques pass through Smem's tq slot), followed by the
+// forward evaluation with that tau.  The references are read from global memory every step in both
+// layouts.
+struct ComputedTorqueTraj {
+    const double *kp, *kd, *qref, *qdref, *qddref, *qbias, *taumax;
+    double* taulast;
+    int64_t qdstride, qddstride;
+    int32_t T, sps;
+};
+
+// Text of its own beside fbd_euler_traj_kernel, for that kernel's reason.  Only the
+// articulated-body path exists (the call refuses mass_reg); ABA stays a parameter so that an
+// instantiation is named like its neighbours'.
+template <int NVMAX, int HW, bool PRI, bool ABA>
+__global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_ctq_kernel(Model m, blf_fb_state st,
+                                                          Contacts ct, int32_t nsteps, double dT, double dT_last,
+                                                          ComputedTorqueTraj law, int64_t batch)
+{
+    static_assert(ABA, "computed torque: the articulated-body path only");
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const Half<HW> H;
+    const int n = m.n, NV = n + 6;
+    constexpr bool kCS = HW == 32;
+    const Smem S(smem + H.half * Smem(nullptr, n, ct.C, ABA).total, n, ct.C, ABA);
+    const int lane = H.hl;
+    constexpr int per = kWave / HW;
+    const Topo T = build_topo<HW>(m, S);
+    double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n | dR 9
+    double* dR = loc + 18 + 2 * n;
+    const int64_t i0 = (int64_t)blockIdx.x * per + H.half;
+    const bool active = i0 < batch;   // see fbd_euler_kernel
+    const int64_t q = active ? i0 : batch - 1;
+    for (int i = lane; i < 18 + 2 * n; i += HW) {
+        double v;
+        if (i < 6) v = st.base_vel[6 * q + i];
+        else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
+        else if (i < 9 + n) {   // the reference point; the position relative to it starts at zero
+            loc[kRef(n) + (i - 6 - n)] = st.base_pos[3 * q + (i - 6 - n)];
+            v = 0.0;
+        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
+        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
+        loc[i] = v;
+    }
+    if constexpr (kCS) {
+        const int C = ct.C;
+        for (int i = lane; i < 29 * C; i += HW) {
+            double v;
+            if (i < C) v = (double)m.flink[ct.frame[i]];
+            else if (i < 13 * C) v = m.fpose[12 * ct.frame[(i - C) / 12] + (i - C) % 12];
+            else if (i < 25 * C) {   // null poses, their positions relative to the reference point
+                const int e = (i - 13 * C) % 12;
+                v = ct.null_pose[(q * C) * 12 + (i - 13 * C)];
+                if (e < 3) v = v - st.base_pos[3 * q + e];
+            }
+            else v = ct.params[i - 25 * C];
+            S.cst()[i] = v;
+        }
+    }
+    wave_sync();
+    bool ok = true;
+    const double zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int32_t step = 0; step < nsteps; ++step) {
+        const double h = step + 1 < nsteps ? dT : dT_last;
+        int64_t slice = step / law.sps;
+        if (slice > law.T - 1) slice = law.T - 1;   // the last slice is held to the end
+        const int64_t at = slice * batch + q;       // element (slice, q, .)
+        // the commanded joint accelerations of this step from its start state
+        for (int j = lane; j < n; j += HW) {
+            double r = law.qref[at * n + j];
+            if (law.qbias) r = r + law.qbias[(int64_t)n * q + j];
+            double a = law.kp[j] * (r - loc[18 + n + j]);
+            if (law.qdref) a = a + law.kd[j] * (law.qdref[at * law.qdstride + j] - loc[6 + j]);
+            else a = a - law.kd[j] * loc[6 + j];
+            if (law.qddref) a = law.qddref[at * law.qddstride + j] + a;
+            S.tq()[j] = a;
+        }
+        wave_sync();
+        double bo[6];
+        ok = fbd_id_eval<HW, PRI, kCS>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n, S.tq(), false,
+                                       zero6, bo, ct, q, T, loc + kRef(n)) && ok;
+        if (law.taumax) {   // (selects: a NaN torque stays NaN)
+            for (int j = lane; j < n; j += HW) {
+                const double t = S.tq()[j], mx = law.taumax[j];
+                S.tq()[j] = t > mx ? mx : t < -mx ? -mx : t;
+            }
+            wave_sync();
+        }
+        ok = fbd_eval<NVMAX, HW, PRI, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
+                                                S.tq(), ct, q, nullptr, T, loc + kRef(n)) && ok;
+        if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, loc + 3, dR);
+        wave_sync();
+        // positions first (they read the old velocities), then the velocities: fbd_euler_kernel
+        for (int i = lane; i < 12 + n; i += HW) {
+            if (i < 3) loc[6 + n + i] = loc[6 + n + i] + loc[i] * h;
+            else if (i < 12) loc[6 + n + i] = loc[6 + n + i] + dR[i - 3] * h;
+            else loc[18 + n + (i - 12)] = loc[18 + n + (i - 12)] + loc[6 + (i - 12)] * h;
+        }
+        wave_sync();
+        for (int i = lane; i < NV; i += HW) loc[i] = loc[i] + S.rhs()[i] * h;
+        wave_sync();
+    }
+    if (active) {
+        const double nan = __builtin_nan("");
+        for (int i = lane; i < 18 + 2 * n; i += HW) {
+            const double v = ok ? loc[i] : nan;
+            if (i < 6) st.base_vel[6 * q + i] = v;
+            else if (i < 6 + n) st.joint_vel[(int64_t)n * q + (i - 6)] = v;
+            else if (i < 9 + n) st.base_pos[3 * q + (i - 6 - n)] = loc[kRef(n) + (i - 6 - n)] + v;
+            else if (i < 18 + n) st.base_rot[9 * q + (i - 9 - n)] = v;
+            else st.joint_pos[(int64_t)n * q + (i - 18 - n)] = v;
+        }
+        if (law.taulast && nsteps > 0)
+            for (int j = lane; j < n; j += HW) law.taulast[(int64_t)n * q + j] = ok ? S.tq()[j] : nan;
+    }
+}
+
 Contacts to_contacts(const blf_fb_contacts* c)
 {
     Contacts o;
@@ -1180,6 +1653,47 @@ blf_status launch_fbd_euler_traj(const blf_fb_model* md, const blf_fb_state* st,
                            to_model(md), *st, c, reg, nsteps, dT, dT_last, imp, batch);
 #undef FBD_TRJ
     return check_hip(hipGetLastError(), "fbd_euler_traj_kernel launch");
+}
+
+blf_status launch_fb_invdyn(const blf_fb_model* md, const blf_fb_state* st, const double* joint_acc,
+                            const double* base_acc, const blf_fb_contacts* ct, int64_t batch, double* tau,
+                            double* bout, int32_t* status, hipStream_t s)
+{
+    if (batch == 0) return BLF_OK;
+    const Contacts c = to_contacts(ct);
+    const bool pri = md->joint_type != nullptr;
+    const size_t lds = fbd_lds_bytes(md->ndof, c.C, true);
+    if (md->ndof + 6 <= 32)   // two systems per wavefront
+        hipLaunchKernelGGL((pri ? fb_invdyn_kernel<32, true> : fb_invdyn_kernel<32, false>),
+                           dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds, s, to_model(md), *st, joint_acc,
+                           base_acc, c, tau, bout, status, batch);
+    else
+        hipLaunchKernelGGL((pri ? fb_invdyn_kernel<kWave, true> : fb_invdyn_kernel<kWave, false>),
+                           dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, joint_acc, base_acc, c, tau,
+                           bout, status, batch);
+    return check_hip(hipGetLastError(), "fb_invdyn_kernel launch");
+}
+
+blf_status launch_fbd_euler_ctq(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
+                                int64_t batch, int32_t nsteps, double dT, double dT_last, hipStream_t s,
+                                const blf_computed_torque_traj* it)
+{
+    if (batch == 0) return BLF_OK;
+    const Contacts c = to_contacts(ct);
+    const ComputedTorqueTraj law{it->kp, it->kd, it->q_ref, it->qd_ref, it->qdd_ref, it->q_bias, it->tau_max,
+                                 it->tau_last, it->qd_stride, it->qdd_stride, it->slices, it->steps_per_slice};
+    const bool pri = md->joint_type != nullptr;
+    const size_t lds = fbd_lds_bytes(md->ndof, c.C, true);
+    if (md->ndof + 6 <= 32)
+        hipLaunchKernelGGL((pri ? fbd_euler_ctq_kernel<32, 32, true, true> : fbd_euler_ctq_kernel<32, 32, false, true>),
+                           dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds, s, to_model(md), *st, c, nsteps,
+                           dT, dT_last, law, batch);
+    else
+        hipLaunchKernelGGL((pri ? fbd_euler_ctq_kernel<BLF_FBD_MAX_DOFS + 6, kWave, true, true>
+                                : fbd_euler_ctq_kernel<BLF_FBD_MAX_DOFS + 6, kWave, false, true>),
+                           dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, c, nsteps, dT, dT_last, law,
+                           batch);
+    return check_hip(hipGetLastError(), "fbd_euler_ctq_kernel launch");
 }
 
 blf_status launch_com_reference(const double* xi0, const double* vrp, int64_t vstride, const double* omega0,

@@ -94,6 +94,8 @@ class FloatingBaseDynamicalSystem
     blf::DeviceBuffer<double> m_dOrigin, m_dRot, m_dAxis, m_dMass, m_dCom, m_dInertia, m_dFramePose;
     blf::DeviceBuffer<double> m_dReg, m_dState, m_dTau, m_dContactParams, m_dNullPose, m_dOut;
     blf::DeviceBuffer<double> m_dContactWrench, m_dFrameOut;
+    blf::DeviceBuffer<double> m_dIdIn, m_dIdOut;   // inverseDynamics: joint accelerations | torques, base acceleration
+    blf::DeviceBuffer<int32_t> m_dIdStatus;
     std::vector<std::shared_ptr<ContactModels::ContactModel>> m_contactModels;
     bool m_hostContacts{false};   /**< a contact model the kernel cannot evaluate */
 
@@ -109,6 +111,19 @@ public:
     bool setRobotModel(const blf::RobotModel& model);
     bool setMassMatrixRegularization(const blf::MatrixXd& matrix);
     bool dynamics(const double& time, StateDerivativeType& stateDerivative) final;
+
+    /**
+     * Inverse dynamics with the base free (blf_fb_inverse_dynamics, free-base mode) at the current
+     * state, with the contact wrenches of the control input (prepared and updated as dynamics()
+     * does; the control input's joint torques are not used): the joint torques that produce
+     * jointAcceleration and the base acceleration (mixed: linear, angular) that goes with them.
+     * Setting those torques as the control input, dynamics() returns jointAcceleration and
+     * baseAcceleration.  The mass-matrix regularization does not enter.
+     * @return false, with a line on std::cerr, if no model is set, a size is wrong or the device
+     * reports a failure of this robot (a non-finite input, a non-positive inertia pivot).
+     */
+    bool inverseDynamics(const blf::VectorXd& jointAcceleration, blf::Vector6& baseAcceleration,
+                         blf::VectorXd& jointTorques);
 
     /** Device hook used by ForwardEuler<FloatingBaseDynamicalSystem>. */
     bool forwardEulerIntegrate(double initialTime, double finalTime, double dT);

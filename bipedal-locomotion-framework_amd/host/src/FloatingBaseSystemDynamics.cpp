@@ -405,6 +405,54 @@ bool FloatingBaseDynamicalSystem::dynamics(const double& time, StateDerivativeTy
     return true;
 }
 
+bool FloatingBaseDynamicalSystem::inverseDynamics(const blf::VectorXd& jointAcceleration,
+                                                  blf::Vector6& baseAcceleration,
+                                                  blf::VectorXd& jointTorques)
+{
+    const char* where = "FloatingBaseDynamicalSystem::inverseDynamics";
+    if (!m_hasModel)
+    {
+        std::cerr << "[" << where << "] Please call 'setRobotModel()' before." << std::endl;
+        return false;
+    }
+    const std::size_t n = m_actuatedDoFs;
+    if (jointAcceleration.size() != n)
+    {
+        std::cerr << "[" << where << "] Wrong size of the joint acceleration: " << jointAcceleration.size()
+                  << ", the model has " << n << " joints." << std::endl;
+        return false;
+    }
+    blf_fb_model model;
+    blf_fb_state state;
+    blf_fb_contacts contacts;
+    blf_handle* h = blf::threadHandle();
+    if (h == nullptr || !prepare(where, model, state, contacts)
+        || !updateContactModels(where, model, state, m_hostContacts))
+        return false;
+    if (!m_dIdIn.upload(jointAcceleration.data(), n) || !m_dIdOut.resize(n + 6) || !m_dIdStatus.resize(1))
+        return false;
+    double* o = m_dIdOut.data();
+    if (!blf::report(blf_fb_inverse_dynamics(h, &model, &state, m_dIdIn.data(), nullptr, &contacts, 1, o, o + n,
+                                             nullptr, m_dIdStatus.data(), 0, nullptr),
+                     where))
+        return false;
+    std::vector<double> host(n + 6);
+    int32_t status = 0;
+    if (!m_dIdOut.download(host.data(), host.size()) || !m_dIdStatus.download(&status, 1)) return false;
+    if (status != BLF_IK_OK)
+    {
+        std::cerr << "[" << where << "] The device reports "
+                  << (status == BLF_IK_BAD_INPUT ? "a non-finite state, acceleration or contact wrench"
+                                                 : "a whole-body inertia that is not positive definite")
+                  << " (status " << status << ")." << std::endl;
+        return false;
+    }
+    jointTorques.resize(n);
+    for (std::size_t i = 0; i < n; ++i) jointTorques[i] = host[i];
+    for (int i = 0; i < 6; ++i) baseAcceleration[i] = host[n + i];
+    return true;
+}
+
 bool FloatingBaseDynamicalSystem::forwardEulerIntegrate(double initialTime, double finalTime,
                                                         double dT)
 {

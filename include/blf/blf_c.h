@@ -103,7 +103,8 @@ const char* blf_last_error(void);
  * point or struct.  blf_swing_foot_eval and blf_so3_eval, and later blf_fb_ik_solve_hard and
  * blf_fb_ik_integrate_hard (section 12b), then blf_fb_ik_solve_limits and
  * blf_fb_ik_integrate_limits (section 12c), then blf_fb_ik_track (section 12d), then blf_fbd_euler_integrate_impedance_traj
- * (section 9) and blf_dcm_com_reference (section 9b), were added within ABI 3 (no existing
+ * (section 9) and blf_dcm_com_reference (section 9b), then blf_fb_inverse_dynamics (section 8b) and
+ * blf_fbd_euler_integrate_computed_torque_traj (section 9), were added within ABI 3 (no existing
  * entry point or struct changed, so the number stays): a caller detects them by symbol
  * (dlsym).  ABI 2 (0.2.0) added the optional pointer fields blf_dcm_mpc_solution.passes and blf_fb_contacts.law / .wrench:
  * a caller built against an older header must zero-initialise these structs (`= {0}`), since the
@@ -527,6 +528,43 @@ blf_status blf_fbd_euler_integrate(blf_handle* handle, const blf_fb_model* model
                                    int64_t batch, double initial_time, double final_time,
                                    double dT, void* stream);
 
+/* ---- 8b. Floating-base inverse dynamics (KinDynComputations::inverseDynamics /
+ *          generalizedBiasForces; the closed form of a TSID with joint-tracking, base-dynamics and
+ *          joint-dynamics tasks under compliant contacts) ---------------------------------------
+ * With M(q) and h(q, nu) the mass matrix and generalized bias forces of section 8 (mixed
+ * representation), w_c contact c's wrench at the current state and J_c its frame's mixed Jacobian,
+ * both exactly as blf_fbd_dynamics forms them (BLF_CONTACT_CONTINUOUS and BLF_CONTACT_WRENCH laws;
+ * contacts NULL or ncontacts == 0: no contact), and sdd = joint_acc [B][n] (NULL: zero):
+ *
+ * Free-base mode (base_acc == NULL): base_acc_out [B][6] (mixed: linear then angular, the layout
+ * of blf_fbd_dynamics' out->base_vel) and joint_torque [B][n] are the unique pair with
+ *     M [nu_dot_B; sdd] + h = sum_c J_c^T w_c + [0; tau].
+ *   base_acc_out and joint_torque are required; base_wrench is not written.
+ *
+ * Given-base mode (base_acc [B][6] given, mixed): joint_torque and base_wrench [B][6] (force then
+ * torque, mixed, at the base origin) are together
+ *     [base_wrench; tau] = M [base_acc; sdd] + h - sum_c J_c^T w_c,
+ *   iDynTree's inverseDynamics.  With base_acc = 0, sdd = 0 and no contacts it is
+ *   generalizedBiasForces; with nu = 0 as well, the gravity torques.  joint_torque and base_wrench
+ *   are required; base_acc_out is not written.
+ *
+ * status [B] (or NULL) is per robot and reuses section 12's codes: BLF_IK_OK (0); BLF_IK_BAD_INPUT
+ * when the robot's state, joint_acc, base_acc or a BLF_CONTACT_WRENCH wrench is not finite;
+ * BLF_IK_NOT_POSITIVE when a pivot of the whole-body 6 x 6 inertia (free-base mode's LDL^T) is
+ * not a finite positive number.  Either gives that robot NaN in every output of its own and touches
+ * no other robot.  An unknown joint_type makes every output NaN, as in section 8.
+ * BLF_ERR_INVALID_ARGUMENT: NULL handle, model, state, model array or (batch > 0) state buffer or
+ * required output, reserved != 0, negative batch.  BLF_ERR_UNSUPPORTED as blf_fbd_dynamics: ndof
+ * outside [1, BLF_FBD_MAX_DOFS], more than BLF_FBD_MAX_CONTACTS contacts.  batch == 0: BLF_OK.
+ * One kernel launch on `stream`, no staged copy and no host synchronisation (capturable).  The
+ * cost is one outward and one inward pass over the tree and a 6 x 6 solve: no mass matrix.        */
+blf_status blf_fb_inverse_dynamics(blf_handle* handle, const blf_fb_model* model,
+                                   const blf_fb_state* state, const double* joint_acc,
+                                   const double* base_acc, const blf_fb_contacts* contacts,
+                                   int64_t batch, double* joint_torque, double* base_acc_out,
+                                   double* base_wrench, int32_t* status, int32_t reserved,
+                                   void* stream);
+
 /* ---- 9. Closed loop (BASELINE.json configs[4]): the maps between the robot and the planner ----
  * The reference has no closed-loop API: a user drives TimeVaryingDCMPlanner::advance()
  * (System/Advanceable.h:24-46) and ForwardEuler<FloatingBaseDynamicalSystem>::integrate
@@ -607,6 +645,52 @@ blf_status blf_fbd_euler_integrate_impedance_traj(blf_handle* handle, const blf_
                                                   const double* mass_reg, int64_t batch,
                                                   double initial_time, double final_time, double dT,
                                                   void* stream);
+
+/* blf_fbd_euler_integrate_computed_torque_traj: blf_fbd_euler_integrate_impedance_traj with the
+ * torque law replaced by computed torque.  The schedule (blf_step_schedule's, the stale last step
+ * included), the slice index s(i) = min(i / steps_per_slice, slices - 1) and the layouts of q_ref,
+ * qd_ref and q_bias are that call's; qdd_ref is strided like qd_ref (NULL: zero).  kp and kd are
+ * ACCELERATION gains (1/s^2 and 1/s).  Before every step, at the step's start state,
+ *   sdd_j = qdd_ref[s][b][j] + kp_j (q_ref[s][b][j] + q_bias[b][j] - q_j) + kd_j (qd_ref[s][b][j] - qdot_j)
+ *   tau   = the joint torques of blf_fb_inverse_dynamics' free-base mode at sdd, with the call's contacts
+ *   tau_j = min(max(tau_j, -tau_max_j), tau_max_j)   when tau_max [n] (finite, > 0) is given
+ * and the step is the forward evaluation of blf_fbd_dynamics with that tau as the control input
+ * (always run, clamped or not: the torque is the actual input) and the Euler update of
+ * blf_fbd_euler_integrate.  Unclamped, every joint then follows
+ *   q_j += h qdot_j,  qdot_j += h sdd_j
+ * whatever the base, the contacts and the other joints do.  The call does not check the gains
+ * against the step: explicit Euler needs the eigenvalues of [[1, h], [-kp h, 1 - kd h]] inside the
+ * unit circle for every step length h of the schedule, the 2 h of a stale last step included; for
+ * kd = 2 sqrt(kp) the condition is sqrt(kp) h < 2.
+ * tau_last [B][n] or NULL: the torque applied at the last step.  A non-finite reference of robot b
+ * gives that robot a NaN state (and tau_last) and touches no other robot; so does a failed pivot
+ * of either evaluation.  Slices past the last one used are never read.
+ * BLF_ERR_INVALID_ARGUMENT: what blf_fbd_euler_integrate_impedance_traj refuses, and qdd_stride < n
+ * with qdd_ref set.  BLF_ERR_UNSUPPORTED: mass_reg != NULL (inverse dynamics is defined without
+ * the regularisation), and what blf_fbd_dynamics refuses as unsupported.                          */
+typedef struct blf_computed_torque_traj {
+    int32_t ndof;                 /* n, must match the model                                 */
+    int32_t slices;               /* T >= 1                                                  */
+    int32_t steps_per_slice;      /* >= 1                                                    */
+    int32_t reserved;             /* must be 0                                               */
+    const double* kp;             /* [n] 1/s^2                                               */
+    const double* kd;             /* [n] 1/s                                                 */
+    const double* q_ref;          /* [T][B][n]                                               */
+    const double* qd_ref;         /* element (t,b,j) at qd_ref[(t*B + b)*qd_stride + j], or NULL */
+    int64_t qd_stride;            /* >= n when qd_ref                                        */
+    const double* qdd_ref;        /* element (t,b,j) at qdd_ref[(t*B + b)*qdd_stride + j], or NULL */
+    int64_t qdd_stride;           /* >= n when qdd_ref                                       */
+    const double* q_bias;         /* [B][n] or NULL: added to every slice                    */
+    const double* tau_max;        /* [n] or NULL: the torque bound, finite and > 0           */
+    double* tau_last;             /* [B][n] or NULL: the last step's applied torque          */
+} blf_computed_torque_traj;
+blf_status blf_fbd_euler_integrate_computed_torque_traj(blf_handle* handle, const blf_fb_model* model,
+                                                        const blf_fb_state* state,
+                                                        const blf_computed_torque_traj* law,
+                                                        const blf_fb_contacts* contacts,
+                                                        const double* mass_reg, int64_t batch,
+                                                        double initial_time, double final_time,
+                                                        double dT, void* stream);
 
 /* ---- 9b. Closed loop: the plan -> centre-of-mass reference map ---------------------------------
  * blf_dcm_com_reference: the set points blf_ik_schedule reads (com_pos, com_vel [B][T][3]) from a

@@ -1,0 +1,142 @@
+"""Timing of the inverse-dynamics kernels (csrc/fb_dynamics.hip: fb_invdyn_kernel, fbd_euler_ctq_kernel) on
+standing humanoids with both soles in contact (diagnostics; not the driver's bench.py).  HIP events around
+`reps` back-to-back calls after a warm-up, median of `rounds` rounds, the variants alternating within a
+round.  One JSON line each:
+
+  * blf_fb_inverse_dynamics (free-base and given-base mode) at B robots, against blf_fbd_dynamics on the
+    articulated-body path with the same contacts and against blf_fb_frame_state (the forward kinematics
+    alone, one robot per wavefront);
+  * blf_fbd_euler_integrate_computed_torque_traj against blf_fbd_euler_integrate_impedance_traj on the same
+    input: 19 steps of 1 ms, 4 distinct slices, qd_ref and q_bias (the state restored before every call by
+    a device copy, timed on its own and subtracted).  The computed-torque call does an inverse and a
+    forward evaluation per step; the impedance call a forward evaluation only.
+
+  timeout -k 10 600 python tools/id_bench.py [--robots 16384] [--rounds 5] [--reps 10]
+(BLF_LIB=.../lib/libblf_<name>.so times a variant build, tools/build_variant.sh)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "bipedal-locomotion-framework_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from blf import closed_loop as DL, native, robot  # noqa: E402
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps   # ms per call
+
+
+def compare(variants, reps, rounds):
+    """{name: fn} -> {name: [median ms, min ms, max ms]}, the variants alternating in every round."""
+    for fn in variants.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            times[k].append(timed(fn, reps))
+    return {k: [statistics.median(v), min(v), max(v)] for k, v in times.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--robots", type=int, default=16384)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--label", default="")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a HIP device"
+    h = native.Handle(0)
+    prov = native.build_provenance()
+    print(json.dumps({"bench": "provenance", "lib_src_hash": prov["lib_src_hash"],
+                      "lib": os.path.basename(prov["lib"]), "matches_tree": prov["matches"],
+                      "device": torch.cuda.get_device_name(0), "label": args.label}), flush=True)
+    B, T = args.robots, 4
+    model = robot.humanoid24()
+    n = model["n"]
+    host = robot.standing_states(model, B, seed=3)
+    law = robot.posture_law_arrays(model)
+    dev = lambda a, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).cuda()
+    dm = h.fb_model(model)
+    start = {k: dev(host[k]) for k in native.FB_STATE_KEYS}
+    st = {k: v.clone() for k, v in start.items()}
+    contacts = dict(frame=dev(np.arange(2), torch.int32), params=dev(np.tile(np.asarray(DL.CONTACT_PARAMS), (2, 1))),
+                    null_pose=dev(robot.sole_null_poses(model, host)))
+    rng = np.random.default_rng(4)
+    sdd, bacc = dev(rng.normal(size=(B, n))), dev(rng.normal(size=(B, 6)))
+    tau, six = torch.empty_like(sdd), torch.empty_like(bacc)
+    status = torch.empty((B,), dtype=torch.int32, device="cuda")
+    zero = torch.zeros_like(sdd)
+    frames = torch.arange(len(model["frame_link"]), dtype=torch.int32, device="cuda")
+    fpose = torch.empty((B, frames.shape[0], 12), dtype=torch.float64, device="cuda")
+    ftwist = torch.empty((B, frames.shape[0], 6), dtype=torch.float64, device="cuda")
+    res = compare({
+        "id_free": lambda: h.fb_inverse_dynamics(dm, start, joint_acc=sdd, contacts=contacts, joint_torque=tau,
+                                                 base_acc_out=six, status=status),
+        "id_given": lambda: h.fb_inverse_dynamics(dm, start, joint_acc=sdd, base_acc=bacc, contacts=contacts,
+                                                  joint_torque=tau, base_wrench=six, status=status),
+        "fbd_dynamics": lambda: h.fbd_dynamics(dm, start, zero, contacts=contacts),
+        "frame_state": lambda: h.fb_frame_state(dm, start, frames, pose=fpose, twist=ftwist)},
+        reps=args.reps, rounds=args.rounds)
+    h.fb_inverse_dynamics(dm, start, joint_acc=sdd, contacts=contacts, joint_torque=tau, base_acc_out=six,
+                          status=status)
+    print(json.dumps({"bench": "fb_inverse_dynamics", "robots": B, "ndof": n, "contacts": 2,
+                      "free_base_ms": res["id_free"], "given_base_ms": res["id_given"],
+                      "fbd_dynamics_aba_ms": res["fbd_dynamics"], "fb_frame_state_ms": res["frame_state"],
+                      "free_over_fbd_dynamics": res["id_free"][0] / res["fbd_dynamics"][0],
+                      "free_over_frame_state": res["id_free"][0] / res["frame_state"][0],
+                      "all_status_ok": bool((status == 0).all()), "label": args.label}), flush=True)
+    # the fused calls: 19 steps of 1 ms, one control period of the closed loop
+    q_ref = dev(host["joint_pos"][None] + rng.normal(size=(T, B, n)) * 0.02)
+    nu = dev(rng.uniform(-0.1, 0.1, (T, B, 6 + n)))
+    q_bias = dev(rng.uniform(-0.01, 0.01, (B, n)))
+    imp = h.joint_impedance_traj(h.joint_impedance(law["kp"], law["kd"]), q_ref, 5, qd_ref=nu, qd_offset=6,
+                                 q_bias=q_bias)
+    ctq = h.computed_torque_traj(400.0, 40.0, q_ref, 5, qd_ref=nu, qd_offset=6, q_bias=q_bias)
+    ctq_clamped = h.computed_torque_traj(400.0, 40.0, q_ref, 5, qd_ref=nu, qd_offset=6, q_bias=q_bias, tau_max=80.0,
+                                         tau_last=True)
+    t1, dT = 0.019, 0.001
+
+    def restore():
+        for k in native.FB_STATE_KEYS:
+            st[k].copy_(start[k])
+
+    def impedance():
+        restore()
+        h.fbd_euler_integrate_impedance_traj(dm, st, imp, 0.0, t1, dT, contacts=contacts)
+
+    def computed(law_):
+        restore()
+        h.fbd_euler_integrate_computed_torque_traj(dm, st, law_, 0.0, t1, dT, contacts=contacts)
+
+    res = compare({"restore": restore, "impedance_traj": impedance, "computed_torque": lambda: computed(ctq),
+                   "computed_torque_clamped": lambda: computed(ctq_clamped)}, reps=args.reps, rounds=args.rounds)
+    computed(ctq)
+    finite = all(bool(torch.isfinite(st[k]).all()) for k in native.FB_STATE_KEYS)
+    r0 = res["restore"][0]
+    net = {k: res[k][0] - r0 for k in ("impedance_traj", "computed_torque", "computed_torque_clamped")}
+    print(json.dumps({"bench": "computed_torque_traj", "robots": B, "steps": 19, "slices": T,
+                      "impedance_traj_ms": res["impedance_traj"], "computed_torque_ms": res["computed_torque"],
+                      "computed_torque_clamped_ms": res["computed_torque_clamped"], "restore_ms": res["restore"],
+                      "computed_over_impedance_net": net["computed_torque"] / net["impedance_traj"],
+                      "clamped_over_impedance_net": net["computed_torque_clamped"] / net["impedance_traj"],
+                      "computed_ms_per_step_net": net["computed_torque"] / 19, "states_finite": finite,
+                      "label": args.label}), flush=True)
+    h.close()
+
+
+if __name__ == "__main__":
+    main()
