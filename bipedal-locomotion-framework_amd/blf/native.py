@@ -1004,27 +1004,30 @@ class Handle:
         CONTACT_WRENCH contacts' (force, torque), mixed representation at the frame).
         Returns the derivative with the same keys (base_vel -> base acceleration, ...)."""
         torch = _torch()
-        B, n = state["joint_pos"].shape
         out = {k: torch.empty_like(state[k]) for k in FB_STATE_KEYS}
-        NV = n + 6
-        reg = _ptr(mass_reg, torch.float64, (NV, NV), "mass_reg") if mass_reg is not None else None
-        st, oc = self._fb_state(state, B, n), self._fb_state(out, B, n)
-        ct = self._fb_contacts(contacts, B)
+        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg)
+        oc = self._fb_state(out, B, n)
         _check(lib().blf_fbd_dynamics(self._h, ctypes.byref(dm.c), ctypes.byref(st),
                                       _ptr(torque, torch.float64, (B, n), "torque"),
                                       ctypes.byref(ct), reg, B, ctypes.byref(oc),
                                       _stream(stream)))
         return out
 
+    def _fbd_args(self, state, contacts, mass_reg, law_batch=None):
+        """What blf_fbd_dynamics and the four blf_fbd_euler_integrate* calls build alike: B, n, the state
+        and contacts structs and the mass_reg pointer (law_batch: the robots a trajectory law holds)."""
+        torch = _torch()
+        B, n = state["joint_pos"].shape
+        if law_batch is not None and law_batch != B:
+            raise ValueError(f"the trajectory holds {law_batch} robots, the state {B}")
+        reg = _ptr(mass_reg, torch.float64, (n + 6, n + 6), "mass_reg") if mass_reg is not None else None
+        return B, n, self._fb_state(state, B, n), self._fb_contacts(contacts, B), reg
+
     def fbd_euler_integrate(self, dm, state, torque, t0, t1, dT, contacts=None, mass_reg=None,
                             stream=None):
         """ForwardEuler<FloatingBaseDynamicalSystem>::integrate in place on `state`."""
         torch = _torch()
-        B, n = state["joint_pos"].shape
-        NV = n + 6
-        reg = _ptr(mass_reg, torch.float64, (NV, NV), "mass_reg") if mass_reg is not None else None
-        st = self._fb_state(state, B, n)
-        ct = self._fb_contacts(contacts, B)
+        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg)
         _check(lib().blf_fbd_euler_integrate(self._h, ctypes.byref(dm.c), ctypes.byref(st),
                                              _ptr(torque, torch.float64, (B, n), "torque"),
                                              ctypes.byref(ct), reg, B, float(t0), float(t1),
@@ -1381,16 +1384,14 @@ class Handle:
         """blf_fbd_euler_integrate_impedance in place on `state`: the control input of every
         Euler step is tau = kp (q_ref - q) - kd qdot (impedance: joint_impedance())."""
         torch = _torch()
-        B, n = state["joint_pos"].shape
-        NV = n + 6
-        reg = _ptr(mass_reg, torch.float64, (NV, NV), "mass_reg") if mass_reg is not None else None
+        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg)
         imp = JointImpedance()
         imp.ndof = n
         imp.kp = _ptr(impedance["kp"], torch.float64, (n,), "kp")
         imp.kd = _ptr(impedance["kd"], torch.float64, (n,), "kd")
         imp.q_ref = _ptr(q_ref, torch.float64, (B, n), "q_ref")
-        args = (self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(imp),
-                ctypes.byref(self._fb_contacts(contacts, B)), reg, B, float(t0), float(t1), float(dT))
+        args = (self._h, ctypes.byref(dm.c), ctypes.byref(st), ctypes.byref(imp), ctypes.byref(ct), reg, B,
+                float(t0), float(t1), float(dT))
         _check(lib().blf_fbd_euler_integrate_impedance(*args, _stream(stream)))
         return state
 
@@ -1427,14 +1428,9 @@ class Handle:
         """blf_fbd_euler_integrate_impedance_traj in place on `state`: integration step i tracks slice
         min(i // steps_per_slice, T - 1) of traj (joint_impedance_traj()),
         tau = kp (q_ref + q_bias - q) - kd (qdot - qd_ref)."""
-        torch = _torch()
-        B, n = state["joint_pos"].shape
-        NV = n + 6
-        if traj.batch != B:
-            raise ValueError(f"the trajectory holds {traj.batch} robots, the state {B}")
-        reg = _ptr(mass_reg, torch.float64, (NV, NV), "mass_reg") if mass_reg is not None else None
-        args = (self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(traj.c),
-                ctypes.byref(self._fb_contacts(contacts, B)), reg, B, float(t0), float(t1), float(dT))
+        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg, traj.batch)
+        args = (self._h, ctypes.byref(dm.c), ctypes.byref(st), ctypes.byref(traj.c), ctypes.byref(ct), reg, B,
+                float(t0), float(t1), float(dT))
         _check(lib().blf_fbd_euler_integrate_impedance_traj(*args, _stream(stream)))
         return state
 
@@ -1495,14 +1491,9 @@ class Handle:
         """blf_fbd_euler_integrate_computed_torque_traj in place on `state`: before every step the torque
         is the free-base inverse dynamics of sdd = qdd_ref + kp (q_ref + q_bias - q) + kd (qd_ref - qdot),
         clamped to tau_max, then the forward step (law: computed_torque_traj()).  mass_reg is refused."""
-        torch = _torch()
-        B, n = state["joint_pos"].shape
-        NV = n + 6
-        if law.batch != B:
-            raise ValueError(f"the trajectory holds {law.batch} robots, the state {B}")
-        reg = _ptr(mass_reg, torch.float64, (NV, NV), "mass_reg") if mass_reg is not None else None
-        args = (self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(law.c),
-                ctypes.byref(self._fb_contacts(contacts, B)), reg, B, float(t0), float(t1), float(dT))
+        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg, law.batch)
+        args = (self._h, ctypes.byref(dm.c), ctypes.byref(st), ctypes.byref(law.c), ctypes.byref(ct), reg, B,
+                float(t0), float(t1), float(dT))
         _check(lib().blf_fbd_euler_integrate_computed_torque_traj(*args, _stream(stream)))
         return state
 

@@ -7,6 +7,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "blf_internal.h"
 
 namespace blf {
@@ -125,6 +127,16 @@ static blf_status step_schedule(double initial_time, double final_time, double d
     return BLF_OK;
 }
 
+// The schedule, then launch(iterations, dT_last): the end of every integrate call
+template <class Launch>
+static blf_status scheduled(double initial_time, double final_time, double dT, Launch launch)
+{
+    int iterations = 0;
+    double dT_last = 0.0;
+    const blf_status st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
+    return st != BLF_OK ? st : launch(iterations, dT_last);
+}
+
 extern "C" {
 
 blf_status blf_create(blf_handle** handle, int32_t device)
@@ -194,12 +206,10 @@ blf_status blf_lti_euler_integrate(blf_handle* handle, int32_t n, int32_t m, con
     BLF_REQUIRE(n >= 1 && m >= 1, "blf_lti_euler_integrate: n=%d m=%d, both must be >= 1", n, m);
     BLF_REQUIRE(batch >= 0, "blf_lti_euler_integrate: negative batch");
     BLF_REQUIRE(batch == 0 || (A && Bm && u && x), "blf_lti_euler_integrate: null buffer");
-    int iterations = 0;
-    double dT_last = 0.0;
-    const blf_status st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
-    if (st != BLF_OK) return st;
-    return launch_lti_euler(n, m, A, Bm, shared_matrices, u, x, batch, iterations, dT, dT_last,
-                            (hipStream_t)stream);
+    return scheduled(initial_time, final_time, dT, [&](int iterations, double dT_last) {
+        return launch_lti_euler(n, m, A, Bm, shared_matrices, u, x, batch, iterations, dT, dT_last,
+                                (hipStream_t)stream);
+    });
 }
 
 blf_status blf_lti_dynamics(blf_handle* handle, int32_t n, int32_t m, const double* A,
@@ -558,12 +568,10 @@ blf_status blf_fbk_euler_integrate(blf_handle* handle, int32_t ndof, double rho,
     BLF_REQUIRE(batch >= 0, "blf_fbk_euler_integrate: negative batch");
     BLF_REQUIRE(batch == 0 || (pos && rot && twist && (ndof == 0 || (joints && joint_vel))),
                 "blf_fbk_euler_integrate: null buffer");
-    int iterations = 0;
-    double dT_last = 0.0;
-    const blf_status st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
-    if (st != BLF_OK) return st;
-    return launch_fbk_euler(ndof, rho, pos, rot, joints, twist, joint_vel, batch, iterations, dT,
-                            dT_last, (hipStream_t)stream);
+    return scheduled(initial_time, final_time, dT, [&](int iterations, double dT_last) {
+        return launch_fbk_euler(ndof, rho, pos, rot, joints, twist, joint_vel, batch, iterations, dT,
+                                dT_last, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"
@@ -676,31 +684,135 @@ blf_status blf_so3_eval(blf_handle* handle, const double* R0, const double* R1,
 
 }  // extern "C"
 
-static blf_status check_fbd(const char* fn, blf_handle* handle, const blf_fb_model* model,
-                            const blf_fb_state* state, const double* tau,
-                            const blf_fb_contacts* contacts, int64_t batch)
+// The argument checks of the floating-base calls (sections 8 to 12d).  A helper holds a run of checks
+// that always come together and takes the entry point's name for its messages.  The order of the checks
+// is part of the interface (tests/test_fb_refusals.py pins which reports first), and so is what differs
+// between the families, which is an argument below, not a consequence of the helper a call reuses:
+//   family      ndof outside [1, 48]              more than 8 contacts       LDS bound, layout
+//   kinematics  INVALID, before batch             -                          -
+//   kForward    INVALID, before batch             INVALID, with C < 0        160 KB, the mass matrix's
+//   kInverse    UNSUPPORTED, after the pointers   UNSUPPORTED, after ndof    80 KB, the articulated body's
+//   IK          UNSUPPORTED, after batch          -                          160 KB, the call's own
+// kinematics: blf_fb_dcm, blf_fb_frame_state.  kForward: blf_fbd_dynamics, blf_fbd_euler_integrate and its
+// _impedance and _impedance_traj forms; the bound is the mass matrix's whatever the call launches.
+// kInverse: blf_fb_inverse_dynamics and the _computed_torque_traj integration; ndof comes after C < 0.
+// IK: the seven blf_fb_ik_* calls; ndof comes before nse3, the bound after the staged copies.
+// The joint torque is an argument of blf_fbd_dynamics and blf_fbd_euler_integrate only, which require
+// it with the state buffers (check_dynamics' `inputs`); the laws of the other calls replace it.
+static blf_status check_model_state(const char* fn, const blf_handle* handle, const blf_fb_model* model,
+                                    const blf_fb_state* state)
 {
     BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
     BLF_REQUIRE(model != nullptr && state != nullptr, "%s: null model / state", fn);
-    BLF_REQUIRE(model->ndof >= 1 && model->ndof <= BLF_FBD_MAX_DOFS, "%s: ndof=%d outside [1, %d]",
-                fn, model->ndof, BLF_FBD_MAX_DOFS);
-    BLF_REQUIRE(batch >= 0, "%s: negative batch", fn);
+    return BLF_OK;
+}
+
+static blf_status check_ndof(const char* fn, const blf_fb_model* model, blf_status refused)
+{
+    if (model->ndof < 1 || model->ndof > BLF_FBD_MAX_DOFS)
+        return set_error(refused, "%s: ndof=%d outside [1, %d]", fn, model->ndof, BLF_FBD_MAX_DOFS);
+    return BLF_OK;
+}
+
+static blf_status check_model_arrays(const char* fn, const blf_fb_model* model)
+{
     BLF_REQUIRE(model->parent && model->joint_origin && model->joint_rot && model->joint_axis &&
                     model->link_mass && model->link_com && model->link_inertia,
                 "%s: null model array", fn);
-    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel && state->base_pos &&
-                               state->base_rot && state->joint_pos && tau),
-                "%s: null state buffer", fn);
+    return BLF_OK;
+}
+
+// Where a family checks ndof (the table): in front of batch as an invalid argument, or after the pointers
+enum NdofOrder { kNdofFirst, kNdofLater };
+
+// The first checks of every call but the IK ones (which check their tasks in between): handle, model
+// and state, ndof where the family checks it in front, batch >= 0, the model arrays.  nframes: the
+// size blf_fb_frame_state checks along with batch (one check, one message).
+static blf_status check_model(const char* fn, const blf_handle* handle, const blf_fb_model* model,
+                              const blf_fb_state* state, NdofOrder order, int64_t batch, const int32_t* nframes = nullptr)
+{
+    blf_status st = check_model_state(fn, handle, model, state);
+    if (st == BLF_OK && order == kNdofFirst) st = check_ndof(fn, model, BLF_ERR_INVALID_ARGUMENT);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch >= 0 && (!nframes || *nframes >= 0), "%s: negative %s", fn, nframes ? "size" : "batch");
+    return check_model_arrays(fn, model);
+}
+
+// Whether the state buffers a call reads are there: positions (the IK solves), velocities, or both
+enum : int { kPos = 1, kVel = 2, kPosVel = kPos | kVel };
+static bool state_given(const blf_fb_state* s, int which)
+{
+    return (!(which & kVel) || (s->base_vel && s->joint_vel)) &&
+           (!(which & kPos) || (s->base_pos && s->base_rot && s->joint_pos));
+}
+
+static blf_status check_lds(const char* fn, size_t bytes, size_t bound = 160 * 1024)
+{
+    if (bytes > bound) return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    return BLF_OK;
+}
+
+struct FbFamily {
+    blf_status sizes;   // what an ndof outside [1, 48] and more than 8 contacts report
+    NdofOrder order;    // kNdofFirst: also the contact count's range in one check; kNdofLater: ndof, then C > 8
+    bool aba;           // the LDS layout the bound is taken of (fbd_lds_bytes)
+    size_t lds;
+};
+constexpr FbFamily kForward{BLF_ERR_INVALID_ARGUMENT, kNdofFirst, false, 160 * 1024};
+constexpr FbFamily kInverse{BLF_ERR_UNSUPPORTED, kNdofLater, true, 160 * 1024 / 2};
+
+static blf_status check_contacts(const char* fn, const blf_fb_model* model, const blf_fb_contacts* contacts,
+                                 int64_t batch, const FbFamily& fam)
+{
     const int C = contacts ? contacts->ncontacts : 0;
-    BLF_REQUIRE(C >= 0 && C <= BLF_FBD_MAX_CONTACTS, "%s: %d contacts outside [0, %d]", fn, C,
-                BLF_FBD_MAX_CONTACTS);
+    if (fam.order == kNdofFirst) {
+        BLF_REQUIRE(C >= 0 && C <= BLF_FBD_MAX_CONTACTS, "%s: %d contacts outside [0, %d]", fn, C,
+                    BLF_FBD_MAX_CONTACTS);
+    } else {
+        BLF_REQUIRE(C >= 0, "%s: %d contacts", fn, C);
+        const blf_status st = check_ndof(fn, model, fam.sizes);
+        if (st != BLF_OK) return st;
+        if (C > BLF_FBD_MAX_CONTACTS)
+            return set_error(fam.sizes, "%s: %d contacts, at most %d", fn, C, BLF_FBD_MAX_CONTACTS);
+    }
     BLF_REQUIRE(C == 0 || (contacts->frame && contacts->params && contacts->null_pose &&
                            model->frame_link && model->frame_pose && model->nframes > 0),
                 "%s: null contact buffer", fn);
     BLF_REQUIRE(C == 0 || contacts->law == nullptr || batch == 0 || contacts->wrench != nullptr,
                 "%s: contact laws given without the wrench buffer", fn);
-    if (fbd_lds_bytes(model->ndof, C) > 160 * 1024)
-        return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    return check_lds(fn, fbd_lds_bytes(model->ndof, C, fam.aba), fam.lds);
+}
+
+// The checks of the dynamics calls (kForward, kInverse).  inputs: whether the pointers the call
+// requires along with the state buffers are there.
+static blf_status check_dynamics(const char* fn, const blf_handle* handle, const blf_fb_model* model,
+                                 const blf_fb_state* state, const blf_fb_contacts* contacts, int64_t batch,
+                                 const FbFamily& fam, bool inputs = true)
+{
+    const blf_status st = check_model(fn, handle, model, state, fam.order, batch);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch == 0 || (state_given(state, kPosVel) && inputs), "%s: null state buffer", fn);
+    return check_contacts(fn, model, contacts, batch, fam);
+}
+
+// The fields the three torque laws share, in the calls' order; what: how the messages name the struct
+template <class Law>
+static blf_status check_law(const char* fn, const char* what, const Law* law, const blf_fb_model* model,
+                            int64_t batch)
+{
+    BLF_REQUIRE(law != nullptr, "%s: null %s", fn, what);
+    BLF_REQUIRE(law->reserved == 0, "%s: reserved must be 0", fn);
+    if constexpr (!std::is_same<Law, blf_joint_impedance>::value) {
+        BLF_REQUIRE(law->slices >= 1 && law->steps_per_slice >= 1,
+                    "%s: slices=%d, steps_per_slice=%d, both must be >= 1", fn, law->slices, law->steps_per_slice);
+    }
+    BLF_REQUIRE(law->kp && law->kd && (batch == 0 || law->q_ref), "%s: null %s array", fn, what);
+    BLF_REQUIRE(model != nullptr && law->ndof == model->ndof, "%s: %s ndof %d != model ndof %d", fn, what,
+                law->ndof, model ? model->ndof : -1);
+    if constexpr (!std::is_same<Law, blf_joint_impedance>::value) {
+        BLF_REQUIRE(law->qd_ref == nullptr || law->qd_stride >= law->ndof, "%s: qd_stride=%lld below ndof=%d", fn,
+                    (long long)law->qd_stride, law->ndof);
+    }
     return BLF_OK;
 }
 
@@ -711,11 +823,10 @@ blf_status blf_fbd_dynamics(blf_handle* handle, const blf_fb_model* model,
                             const blf_fb_contacts* contacts, const double* mass_reg,
                             int64_t batch, const blf_fb_state* out, void* stream)
 {
-    blf_status st = check_fbd("blf_fbd_dynamics", handle, model, state, joint_torque, contacts, batch);
+    const char* fn = "blf_fbd_dynamics";
+    const blf_status st = check_dynamics(fn, handle, model, state, contacts, batch, kForward, joint_torque != nullptr);
     if (st != BLF_OK) return st;
-    BLF_REQUIRE(out != nullptr && (batch == 0 || (out->base_vel && out->joint_vel && out->base_pos &&
-                                                  out->base_rot && out->joint_pos)),
-                "blf_fbd_dynamics: null output buffer");
+    BLF_REQUIRE(out != nullptr && (batch == 0 || state_given(out, kPosVel)), "%s: null output buffer", fn);
     return launch_fbd_dynamics(model, state, joint_torque, contacts, mass_reg, batch, out,
                                (hipStream_t)stream);
 }
@@ -724,19 +835,12 @@ blf_status blf_fb_dcm(blf_handle* handle, const blf_fb_model* model, const blf_f
                       const double* omega0, int64_t omega0_stride, int64_t batch, double* com,
                       double* xi, void* stream)
 {
-    BLF_REQUIRE(handle != nullptr, "blf_fb_dcm: null handle");
-    BLF_REQUIRE(model != nullptr && state != nullptr, "blf_fb_dcm: null model / state");
-    BLF_REQUIRE(model->ndof >= 1 && model->ndof <= BLF_FBD_MAX_DOFS, "blf_fb_dcm: ndof=%d outside [1, %d]",
-                model->ndof, BLF_FBD_MAX_DOFS);
-    BLF_REQUIRE(batch >= 0, "blf_fb_dcm: negative batch");
-    BLF_REQUIRE(model->parent && model->joint_origin && model->joint_rot && model->joint_axis &&
-                    model->link_mass && model->link_com && model->link_inertia,
-                "blf_fb_dcm: null model array");
-    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel && state->base_pos &&
-                               state->base_rot && state->joint_pos && com),
-                "blf_fb_dcm: null state / output buffer");
-    BLF_REQUIRE(xi == nullptr || omega0 != nullptr, "blf_fb_dcm: xi requested without omega0");
-    BLF_REQUIRE(omega0_stride >= 0, "blf_fb_dcm: negative omega0 stride");
+    const char* fn = "blf_fb_dcm";
+    const blf_status st = check_model(fn, handle, model, state, kNdofFirst, batch);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(batch == 0 || (state_given(state, kPosVel) && com), "%s: null state / output buffer", fn);
+    BLF_REQUIRE(xi == nullptr || omega0 != nullptr, "%s: xi requested without omega0", fn);
+    BLF_REQUIRE(omega0_stride >= 0, "%s: negative omega0 stride", fn);
     return launch_fb_dcm(model, state, omega0, omega0_stride, batch, com, xi, (hipStream_t)stream);
 }
 
@@ -744,20 +848,13 @@ blf_status blf_fb_frame_state(blf_handle* handle, const blf_fb_model* model,
                               const blf_fb_state* state, int32_t nframes, const int32_t* frames,
                               int64_t batch, double* pose, double* twist, void* stream)
 {
-    BLF_REQUIRE(handle != nullptr, "blf_fb_frame_state: null handle");
-    BLF_REQUIRE(model != nullptr && state != nullptr, "blf_fb_frame_state: null model / state");
-    BLF_REQUIRE(model->ndof >= 1 && model->ndof <= BLF_FBD_MAX_DOFS,
-                "blf_fb_frame_state: ndof=%d outside [1, %d]", model->ndof, BLF_FBD_MAX_DOFS);
-    BLF_REQUIRE(batch >= 0 && nframes >= 0, "blf_fb_frame_state: negative size");
-    BLF_REQUIRE(model->parent && model->joint_origin && model->joint_rot && model->joint_axis &&
-                    model->link_mass && model->link_com && model->link_inertia,
-                "blf_fb_frame_state: null model array");
+    const char* fn = "blf_fb_frame_state";
+    const blf_status st = check_model(fn, handle, model, state, kNdofFirst, batch, &nframes);
+    if (st != BLF_OK) return st;
     BLF_REQUIRE(nframes == 0 || (frames && model->frame_link && model->frame_pose && model->nframes > 0),
-                "blf_fb_frame_state: null frame buffer");
-    BLF_REQUIRE(batch == 0 || nframes == 0 ||
-                    ((pose || twist) && state->base_vel && state->joint_vel && state->base_pos &&
-                     state->base_rot && state->joint_pos),
-                "blf_fb_frame_state: null state / output buffer");
+                "%s: null frame buffer", fn);
+    BLF_REQUIRE(batch == 0 || nframes == 0 || ((pose || twist) && state_given(state, kPosVel)),
+                "%s: null state / output buffer", fn);
     return launch_fb_frame_state(model, state, nframes, frames, batch, pose, twist,
                                  (hipStream_t)stream);
 }
@@ -785,23 +882,14 @@ blf_status blf_fbd_euler_integrate_impedance(blf_handle* handle, const blf_fb_mo
                                              double initial_time, double final_time, double dT,
                                              void* stream)
 {
-    BLF_REQUIRE(impedance != nullptr, "blf_fbd_euler_integrate_impedance: null impedance");
-    BLF_REQUIRE(impedance->reserved == 0, "blf_fbd_euler_integrate_impedance: reserved must be 0");
-    BLF_REQUIRE(impedance->kp && impedance->kd && (batch == 0 || impedance->q_ref),
-                "blf_fbd_euler_integrate_impedance: null impedance array");
-    BLF_REQUIRE(model != nullptr && impedance->ndof == model->ndof,
-                "blf_fbd_euler_integrate_impedance: impedance ndof %d != model ndof %d",
-                impedance->ndof, model ? model->ndof : -1);
-    // the constant-torque checks with a stand-in torque pointer (the impedance replaces it)
-    blf_status st = check_fbd("blf_fbd_euler_integrate_impedance", handle, model, state,
-                              impedance->kp, contacts, batch);
+    const char* fn = "blf_fbd_euler_integrate_impedance";
+    blf_status st = check_law(fn, "impedance", impedance, model, batch);
+    if (st == BLF_OK) st = check_dynamics(fn, handle, model, state, contacts, batch, kForward);
     if (st != BLF_OK) return st;
-    int iterations = 0;
-    double dT_last = 0.0;
-    st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
-    if (st != BLF_OK) return st;
-    return launch_fbd_euler(model, state, nullptr, contacts, mass_reg, batch, iterations, dT,
-                            dT_last, (hipStream_t)stream, impedance);
+    return scheduled(initial_time, final_time, dT, [&](int iterations, double dT_last) {
+        return launch_fbd_euler(model, state, nullptr, contacts, mass_reg, batch, iterations, dT, dT_last,
+                                (hipStream_t)stream, impedance);
+    });
 }
 
 blf_status blf_fbd_euler_integrate_impedance_traj(blf_handle* handle, const blf_fb_model* model,
@@ -813,61 +901,14 @@ blf_status blf_fbd_euler_integrate_impedance_traj(blf_handle* handle, const blf_
                                                   void* stream)
 {
     const char* fn = "blf_fbd_euler_integrate_impedance_traj";
-    BLF_REQUIRE(impedance != nullptr, "%s: null impedance", fn);
-    BLF_REQUIRE(impedance->reserved == 0, "%s: reserved must be 0", fn);
-    BLF_REQUIRE(impedance->slices >= 1 && impedance->steps_per_slice >= 1,
-                "%s: slices=%d, steps_per_slice=%d, both must be >= 1", fn, impedance->slices,
-                impedance->steps_per_slice);
-    BLF_REQUIRE(impedance->kp && impedance->kd && (batch == 0 || impedance->q_ref),
-                "%s: null impedance array", fn);
-    BLF_REQUIRE(model != nullptr && impedance->ndof == model->ndof, "%s: impedance ndof %d != model ndof %d",
-                fn, impedance->ndof, model ? model->ndof : -1);
-    BLF_REQUIRE(impedance->qd_ref == nullptr || impedance->qd_stride >= impedance->ndof,
-                "%s: qd_stride=%lld below ndof=%d", fn, (long long)impedance->qd_stride, impedance->ndof);
-    // the constant-torque checks with a stand-in torque pointer (the impedance replaces it)
-    blf_status st = check_fbd(fn, handle, model, state, impedance->kp, contacts, batch);
+    blf_status st = check_law(fn, "impedance", impedance, model, batch);
+    if (st == BLF_OK) st = check_dynamics(fn, handle, model, state, contacts, batch, kForward);
     if (st != BLF_OK) return st;
-    int iterations = 0;
-    double dT_last = 0.0;
-    st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
-    if (st != BLF_OK) return st;
-    return launch_fbd_euler_traj(model, state, contacts, mass_reg, batch, iterations, dT, dT_last,
-                                 (hipStream_t)stream, impedance);
+    return scheduled(initial_time, final_time, dT, [&](int iterations, double dT_last) {
+        return launch_fbd_euler_traj(model, state, contacts, mass_reg, batch, iterations, dT, dT_last,
+                                     (hipStream_t)stream, impedance);
+    });
 }
-
-}  // extern "C"
-
-// The checks of section 8b and the computed-torque call: invalid arguments first, then the sizes
-// the kernels are not built for (BLF_ERR_UNSUPPORTED, as the whole-body IK calls report them).
-static blf_status check_invdyn(const char* fn, blf_handle* handle, const blf_fb_model* model,
-                               const blf_fb_state* state, const blf_fb_contacts* contacts, int64_t batch)
-{
-    BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
-    BLF_REQUIRE(model != nullptr && state != nullptr, "%s: null model / state", fn);
-    BLF_REQUIRE(batch >= 0, "%s: negative batch", fn);
-    BLF_REQUIRE(model->parent && model->joint_origin && model->joint_rot && model->joint_axis &&
-                    model->link_mass && model->link_com && model->link_inertia,
-                "%s: null model array", fn);
-    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel && state->base_pos && state->base_rot &&
-                               state->joint_pos),
-                "%s: null state buffer", fn);
-    const int C = contacts ? contacts->ncontacts : 0;
-    BLF_REQUIRE(C >= 0, "%s: %d contacts", fn, C);
-    if (model->ndof < 1 || model->ndof > BLF_FBD_MAX_DOFS)
-        return set_error(BLF_ERR_UNSUPPORTED, "%s: ndof=%d outside [1, %d]", fn, model->ndof, BLF_FBD_MAX_DOFS);
-    if (C > BLF_FBD_MAX_CONTACTS)
-        return set_error(BLF_ERR_UNSUPPORTED, "%s: %d contacts, at most %d", fn, C, BLF_FBD_MAX_CONTACTS);
-    BLF_REQUIRE(C == 0 || (contacts->frame && contacts->params && contacts->null_pose &&
-                           model->frame_link && model->frame_pose && model->nframes > 0),
-                "%s: null contact buffer", fn);
-    BLF_REQUIRE(C == 0 || contacts->law == nullptr || batch == 0 || contacts->wrench != nullptr,
-                "%s: contact laws given without the wrench buffer", fn);
-    if (fbd_lds_bytes(model->ndof, C, true) > 160 * 1024 / 2)
-        return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
-    return BLF_OK;
-}
-
-extern "C" {
 
 blf_status blf_fb_inverse_dynamics(blf_handle* handle, const blf_fb_model* model,
                                    const blf_fb_state* state, const double* joint_acc,
@@ -878,7 +919,7 @@ blf_status blf_fb_inverse_dynamics(blf_handle* handle, const blf_fb_model* model
 {
     const char* fn = "blf_fb_inverse_dynamics";
     BLF_REQUIRE(reserved == 0, "%s: reserved must be 0", fn);
-    blf_status st = check_invdyn(fn, handle, model, state, contacts, batch);
+    const blf_status st = check_dynamics(fn, handle, model, state, contacts, batch, kInverse);
     if (st != BLF_OK) return st;
     double* const bout = base_acc ? base_wrench : base_acc_out;
     BLF_REQUIRE(batch == 0 || (joint_torque && bout), "%s: null %s", fn,
@@ -896,26 +937,17 @@ blf_status blf_fbd_euler_integrate_computed_torque_traj(blf_handle* handle, cons
                                                         double dT, void* stream)
 {
     const char* fn = "blf_fbd_euler_integrate_computed_torque_traj";
-    BLF_REQUIRE(law != nullptr, "%s: null law", fn);
-    BLF_REQUIRE(law->reserved == 0, "%s: reserved must be 0", fn);
-    BLF_REQUIRE(law->slices >= 1 && law->steps_per_slice >= 1, "%s: slices=%d, steps_per_slice=%d, both must be >= 1",
-                fn, law->slices, law->steps_per_slice);
-    BLF_REQUIRE(law->kp && law->kd && (batch == 0 || law->q_ref), "%s: null law array", fn);
-    BLF_REQUIRE(model != nullptr && law->ndof == model->ndof, "%s: law ndof %d != model ndof %d", fn, law->ndof,
-                model ? model->ndof : -1);
-    BLF_REQUIRE(law->qd_ref == nullptr || law->qd_stride >= law->ndof, "%s: qd_stride=%lld below ndof=%d", fn,
-                (long long)law->qd_stride, law->ndof);
+    blf_status st = check_law(fn, "law", law, model, batch);
+    if (st != BLF_OK) return st;
     BLF_REQUIRE(law->qdd_ref == nullptr || law->qdd_stride >= law->ndof, "%s: qdd_stride=%lld below ndof=%d", fn,
                 (long long)law->qdd_stride, law->ndof);
-    blf_status st = check_invdyn(fn, handle, model, state, contacts, batch);
+    st = check_dynamics(fn, handle, model, state, contacts, batch, kInverse);
     if (st != BLF_OK) return st;
     if (mass_reg != nullptr)
         return set_error(BLF_ERR_UNSUPPORTED, "%s: mass_reg given (inverse dynamics is defined without it)", fn);
-    int iterations = 0;
-    double dT_last = 0.0;
-    st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
-    if (st != BLF_OK) return st;
-    return launch_fbd_euler_ctq(model, state, contacts, batch, iterations, dT, dT_last, (hipStream_t)stream, law);
+    return scheduled(initial_time, final_time, dT, [&](int iterations, double dT_last) {
+        return launch_fbd_euler_ctq(model, state, contacts, batch, iterations, dT, dT_last, (hipStream_t)stream, law);
+    });
 }
 
 blf_status blf_dcm_com_reference(blf_handle* handle, const double* xi0, const double* vrp,
@@ -941,15 +973,13 @@ blf_status blf_fbd_euler_integrate(blf_handle* handle, const blf_fb_model* model
                                    int64_t batch, double initial_time, double final_time,
                                    double dT, void* stream)
 {
-    blf_status st = check_fbd("blf_fbd_euler_integrate", handle, model, state, joint_torque,
-                              contacts, batch);
+    const blf_status st = check_dynamics("blf_fbd_euler_integrate", handle, model, state, contacts, batch, kForward,
+                                         joint_torque != nullptr);
     if (st != BLF_OK) return st;
-    int iterations = 0;
-    double dT_last = 0.0;
-    st = step_schedule(initial_time, final_time, dT, &iterations, &dT_last);
-    if (st != BLF_OK) return st;
-    return launch_fbd_euler(model, state, joint_torque, contacts, mass_reg, batch, iterations, dT,
-                            dT_last, (hipStream_t)stream);
+    return scheduled(initial_time, final_time, dT, [&](int iterations, double dT_last) {
+        return launch_fbd_euler(model, state, joint_torque, contacts, mass_reg, batch, iterations, dT, dT_last,
+                                (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"
@@ -963,21 +993,19 @@ static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_mode
                            const blf_fb_state* state, const blf_ik_tasks* t, int64_t batch,
                            hipStream_t s, double* wout = nullptr, bool setpoints = true)
 {
-    BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
-    BLF_REQUIRE(model != nullptr && state != nullptr, "%s: null model / state", fn);
+    blf_status st = check_model_state(fn, handle, model, state);
+    if (st != BLF_OK) return st;
     BLF_REQUIRE(t != nullptr, "%s: null tasks", fn);
     BLF_REQUIRE(t->reserved == 0, "%s: tasks->reserved must be 0", fn);
     BLF_REQUIRE(batch >= 0, "%s: negative batch", fn);
-    if (model->ndof < 1 || model->ndof > BLF_FBD_MAX_DOFS)
-        return set_error(BLF_ERR_UNSUPPORTED, "%s: ndof=%d outside [1, %d]", fn, model->ndof,
-                         BLF_FBD_MAX_DOFS);
+    st = check_ndof(fn, model, BLF_ERR_UNSUPPORTED);
+    if (st != BLF_OK) return st;
     if (t->nse3 < 0 || t->nse3 > BLF_IK_MAX_SE3_TASKS)
         return set_error(BLF_ERR_UNSUPPORTED, "%s: nse3=%d outside [0, %d]", fn, t->nse3,
                          BLF_IK_MAX_SE3_TASKS);
     const int n = model->ndof, K = t->nse3;
-    BLF_REQUIRE(model->parent && model->joint_origin && model->joint_rot && model->joint_axis &&
-                    model->link_mass && model->link_com && model->link_inertia,
-                "%s: null model array", fn);
+    st = check_model_arrays(fn, model);
+    if (st != BLF_OK) return st;
     BLF_REQUIRE(K == 0 || (t->frame && t->se3_weight && t->se3_kp && model->frame_link &&
                            model->frame_pose && model->nframes > 0),
                 "%s: null SE3 task array", fn);
@@ -987,7 +1015,7 @@ static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_mode
     BLF_REQUIRE(t->com_weight == nullptr || (std::isfinite(t->com_kp) && t->com_kp >= 0.0),
                 "%s: com_kp=%g, must be finite and >= 0", fn, t->com_kp);
     if (batch == 0) return BLF_OK;
-    BLF_REQUIRE(state->base_pos && state->base_rot && state->joint_pos, "%s: null state buffer", fn);
+    BLF_REQUIRE(state_given(state, kPos), "%s: null state buffer", fn);
     BLF_REQUIRE(!setpoints || K == 0 || t->se3_pose, "%s: null se3_pose", fn);
     BLF_REQUIRE(!setpoints || t->com_weight == nullptr || t->com_pos, "%s: com_weight given without com_pos", fn);
     BLF_REQUIRE(t->joint_pos != nullptr, "%s: null joint_pos set point", fn);
@@ -1000,14 +1028,13 @@ static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_mode
     int at = 0;
     for (const auto& p : parts) {
         if (p.count > 0) {
-            const blf_status st = check_hip(
-                hipMemcpyAsync(hbuf + at, p.src, sizeof(double) * p.count, hipMemcpyDeviceToHost, s),
-                "blf_fb_ik: staging the task weights");
+            st = check_hip(hipMemcpyAsync(hbuf + at, p.src, sizeof(double) * p.count, hipMemcpyDeviceToHost, s),
+                           "blf_fb_ik: staging the task weights");
             if (st != BLF_OK) return st;
         }
         at += p.count;
     }
-    const blf_status st = check_hip(hipStreamSynchronize(s), "blf_fb_ik: staging the task weights");
+    st = check_hip(hipStreamSynchronize(s), "blf_fb_ik: staging the task weights");
     if (st != BLF_OK) return st;
     const int jw0 = 8 * K + (com ? 3 : 0);
     for (int i = 0; i < at; ++i) {
@@ -1020,8 +1047,8 @@ static blf_status check_ik(const char* fn, blf_handle* handle, const blf_fb_mode
                     i < 6 * K ? i : i < 8 * K ? i - 6 * K : i < jw0 ? i - 8 * K : positive ? i - jw0 : i - jw0 - n,
                     v, positive ? "> 0" : ">= 0");
     }
-    if (fb_ik_lds_bytes(n, K) > 160 * 1024)
-        return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    st = check_lds(fn, fb_ik_lds_bytes(n, K));
+    if (st != BLF_OK) return st;
     if (wout)
         for (int i = 0; i < jw0; ++i) wout[i] = hbuf[i];
     return BLF_OK;
@@ -1064,14 +1091,20 @@ static blf_status check_ik_hard(const char* fn, blf_handle* handle, const blf_fb
     return BLF_OK;
 }
 
-// Section 12c's checks (after check_ik_hard's, batch > 0): the struct's scalars, then the limit arrays
-// through a staged copy like check_ik's.  Leaves the default in *max_iter when the caller gave 0.
-static blf_status check_ik_limits(const char* fn, const blf_ik_limits* lim, int n, hipStream_t s, int32_t* max_iter)
+// Section 12c's checks after check_ik_hard's: the struct's scalars (any batch) ...
+static blf_status check_ik_limits_scalars(const char* fn, const blf_ik_limits* lim)
 {
     BLF_REQUIRE(lim->reserved == 0, "%s: limits->reserved must be 0", fn);
     BLF_REQUIRE(std::isfinite(lim->sampling_time) && lim->sampling_time > 0.0,
                 "%s: sampling_time=%g, must be finite and positive", fn, lim->sampling_time);
     BLF_REQUIRE(lim->max_iter >= 0, "%s: max_iter=%d, must be >= 0", fn, lim->max_iter);
+    return BLF_OK;
+}
+
+// ... and, when batch > 0, the limit arrays through a staged copy like check_ik's.  Leaves the default
+// in *max_iter when the caller gave 0.
+static blf_status check_ik_limits(const char* fn, const blf_ik_limits* lim, int n, hipStream_t s, int32_t* max_iter)
+{
     BLF_REQUIRE(lim->pos_lower && lim->pos_upper && lim->klim, "%s: null limit array", fn);
     double hbuf[4 * BLF_FBD_MAX_DOFS];
     const double* src[4] = {lim->pos_lower, lim->pos_upper, lim->klim, lim->vel_max};
@@ -1096,6 +1129,14 @@ static blf_status check_ik_limits(const char* fn, const blf_ik_limits* lim, int 
     return BLF_OK;
 }
 
+// The first checks of the three blf_fb_ik_integrate* calls
+static blf_status check_steps_dt(const char* fn, int32_t steps, double dT)
+{
+    BLF_REQUIRE(steps >= 1, "%s: steps=%d, must be >= 1", fn, steps);
+    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "%s: dT=%g, must be finite and positive", fn, dT);
+    return BLF_OK;
+}
+
 // blf_fb_ik_solve_limits (steps == 0) and blf_fb_ik_integrate_limits after their own argument checks
 static blf_status ik_limits_call(const char* fn, blf_handle* handle, const blf_fb_model* model,
                                  const blf_fb_state* state, const blf_ik_tasks* tasks, const blf_ik_hard* hard,
@@ -1107,20 +1148,13 @@ static blf_status ik_limits_call(const char* fn, blf_handle* handle, const blf_f
     const blf_status st = check_ik_hard(fn, handle, model, state, tasks, hard, batch, s, &slots, &tau);
     if (st != BLF_OK) return st;
     BLF_REQUIRE(batch == 0 || steps > 0 || nu != nullptr, "%s: null nu", fn);
-    BLF_REQUIRE(batch == 0 || steps == 0 || (state->base_vel && state->joint_vel), "%s: null state buffer", fn);
+    BLF_REQUIRE(batch == 0 || steps == 0 || state_given(state, kVel), "%s: null state buffer", fn);
     if (limits == nullptr) return launch_fb_ik(model, state, tasks, batch, steps, dT, nu, status, s, slots, tau);
     blf_ik_limits lim = *limits;
-    if (batch > 0) {
-        const blf_status sl = check_ik_limits(fn, limits, model->ndof, s, &lim.max_iter);
-        if (sl != BLF_OK) return sl;
-        if (fb_ik_lds_bytes(model->ndof, tasks->nse3, true) > 160 * 1024)
-            return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
-    } else {
-        BLF_REQUIRE(limits->reserved == 0, "%s: limits->reserved must be 0", fn);
-        BLF_REQUIRE(std::isfinite(limits->sampling_time) && limits->sampling_time > 0.0,
-                    "%s: sampling_time=%g, must be finite and positive", fn, limits->sampling_time);
-        BLF_REQUIRE(limits->max_iter >= 0, "%s: max_iter=%d, must be >= 0", fn, limits->max_iter);
-    }
+    blf_status sl = check_ik_limits_scalars(fn, limits);
+    if (sl == BLF_OK && batch > 0) sl = check_ik_limits(fn, limits, model->ndof, s, &lim.max_iter);
+    if (sl == BLF_OK && batch > 0) sl = check_lds(fn, fb_ik_lds_bytes(model->ndof, tasks->nse3, true));
+    if (sl != BLF_OK) return sl;
     return launch_fb_ik_limits(model, state, tasks, &lim, batch, steps, dT, nu, status, iters, active, s, slots, tau);
 }
 
@@ -1140,10 +1174,11 @@ blf_status blf_fb_ik_integrate_limits(blf_handle* handle, const blf_fb_model* mo
                                       const blf_ik_limits* limits, int64_t batch, int32_t steps, double dT,
                                       double* nu, int32_t* status, int32_t* iters, uint64_t* active, void* stream)
 {
-    BLF_REQUIRE(steps >= 1, "blf_fb_ik_integrate_limits: steps=%d, must be >= 1", steps);
-    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_fb_ik_integrate_limits: dT=%g, must be finite and positive", dT);
-    return ik_limits_call("blf_fb_ik_integrate_limits", handle, model, state, tasks, hard, limits, batch, steps, dT,
-                          nu, status, iters, active, (hipStream_t)stream);
+    const char* fn = "blf_fb_ik_integrate_limits";
+    const blf_status st = check_steps_dt(fn, steps, dT);
+    if (st != BLF_OK) return st;
+    return ik_limits_call(fn, handle, model, state, tasks, hard, limits, batch, steps, dT, nu, status, iters, active,
+                          (hipStream_t)stream);
 }
 
 blf_status blf_fb_ik_track(blf_handle* handle, const blf_fb_model* model, const blf_fb_state* state,
@@ -1155,12 +1190,13 @@ blf_status blf_fb_ik_track(blf_handle* handle, const blf_fb_model* model, const 
     const char* fn = "blf_fb_ik_track";
     hipStream_t s = (hipStream_t)stream;
     BLF_REQUIRE(schedule != nullptr, "%s: null schedule", fn);
+    // (check_steps_dt's two checks, with schedule->reserved between them)
     BLF_REQUIRE(schedule->steps >= 1, "%s: steps=%d, must be >= 1", fn, schedule->steps);
     BLF_REQUIRE(schedule->reserved == 0 && schedule->reserved2 == 0u, "%s: schedule->reserved must be 0", fn);
     BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "%s: dT=%g, must be finite and positive", fn, dT);
     uint32_t slots = 0;
     double tau = 0.0, w[8 * BLF_IK_MAX_SE3_TASKS + 3];
-    const blf_status st = check_ik_hard(fn, handle, model, state, tasks, hard, batch, s, &slots, &tau, w, false);
+    blf_status st = check_ik_hard(fn, handle, model, state, tasks, hard, batch, s, &slots, &tau, w, false);
     if (st != BLF_OK) return st;
     const int K = tasks->nse3;
     const uint32_t stance = schedule->stance_rows;
@@ -1173,22 +1209,17 @@ blf_status blf_fb_ik_track(blf_handle* handle, const blf_fb_model* model, const 
     blf_ik_limits lim;
     if (limits != nullptr) {
         lim = *limits;
-        BLF_REQUIRE(limits->reserved == 0, "%s: limits->reserved must be 0", fn);
-        BLF_REQUIRE(std::isfinite(limits->sampling_time) && limits->sampling_time > 0.0,
-                    "%s: sampling_time=%g, must be finite and positive", fn, limits->sampling_time);
-        BLF_REQUIRE(limits->max_iter >= 0, "%s: max_iter=%d, must be >= 0", fn, limits->max_iter);
+        st = check_ik_limits_scalars(fn, limits);
+        if (st != BLF_OK) return st;
     }
     if (batch == 0) return BLF_OK;
-    BLF_REQUIRE(state->base_vel && state->joint_vel, "%s: null state buffer", fn);
+    BLF_REQUIRE(state_given(state, kVel), "%s: null state buffer", fn);
     BLF_REQUIRE(K == 0 || schedule->se3_pose, "%s: null schedule->se3_pose", fn);
     BLF_REQUIRE(tasks->com_weight == nullptr || schedule->com_pos, "%s: com_weight given without schedule->com_pos",
                 fn);
-    if (limits != nullptr) {
-        const blf_status sl = check_ik_limits(fn, limits, model->ndof, s, &lim.max_iter);
-        if (sl != BLF_OK) return sl;
-    }
-    if (fb_ik_track_lds_bytes(model->ndof, K) > 160 * 1024)
-        return set_error(BLF_ERR_UNSUPPORTED, "%s: model too large for one workgroup's LDS", fn);
+    if (limits != nullptr) st = check_ik_limits(fn, limits, model->ndof, s, &lim.max_iter);
+    if (st == BLF_OK) st = check_lds(fn, fb_ik_track_lds_bytes(model->ndof, K));
+    if (st != BLF_OK) return st;
     // tau of a call without `hard`: the default (stance rows may still be hard)
     return launch_fb_ik_track(model, state, tasks, limits ? &lim : nullptr, schedule, batch, dT, joint_traj,
                               base_traj, nu_traj, status, fail_step, iters, active, s, slots, stance,
@@ -1209,11 +1240,11 @@ blf_status blf_fb_ik_integrate(blf_handle* handle, const blf_fb_model* model, co
                                const blf_ik_tasks* tasks, int64_t batch, int32_t steps, double dT,
                                double* nu, int32_t* status, void* stream)
 {
-    BLF_REQUIRE(steps >= 1, "blf_fb_ik_integrate: steps=%d, must be >= 1", steps);
-    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_fb_ik_integrate: dT=%g, must be finite and positive", dT);
-    const blf_status st = check_ik("blf_fb_ik_integrate", handle, model, state, tasks, batch, (hipStream_t)stream);
+    const char* fn = "blf_fb_ik_integrate";
+    blf_status st = check_steps_dt(fn, steps, dT);
+    if (st == BLF_OK) st = check_ik(fn, handle, model, state, tasks, batch, (hipStream_t)stream);
     if (st != BLF_OK) return st;
-    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel), "blf_fb_ik_integrate: null state buffer");
+    BLF_REQUIRE(batch == 0 || state_given(state, kVel), "%s: null state buffer", fn);
     return launch_fb_ik(model, state, tasks, batch, steps, dT, nu, status, (hipStream_t)stream);
 }
 
@@ -1234,14 +1265,13 @@ blf_status blf_fb_ik_integrate_hard(blf_handle* handle, const blf_fb_model* mode
                                     const blf_ik_tasks* tasks, const blf_ik_hard* hard, int64_t batch,
                                     int32_t steps, double dT, double* nu, int32_t* status, void* stream)
 {
-    BLF_REQUIRE(steps >= 1, "blf_fb_ik_integrate_hard: steps=%d, must be >= 1", steps);
-    BLF_REQUIRE(std::isfinite(dT) && dT > 0.0, "blf_fb_ik_integrate_hard: dT=%g, must be finite and positive", dT);
+    const char* fn = "blf_fb_ik_integrate_hard";
     uint32_t slots = 0;
     double tau = 0.0;
-    const blf_status st = check_ik_hard("blf_fb_ik_integrate_hard", handle, model, state, tasks, hard, batch,
-                                        (hipStream_t)stream, &slots, &tau);
+    blf_status st = check_steps_dt(fn, steps, dT);
+    if (st == BLF_OK) st = check_ik_hard(fn, handle, model, state, tasks, hard, batch, (hipStream_t)stream, &slots, &tau);
     if (st != BLF_OK) return st;
-    BLF_REQUIRE(batch == 0 || (state->base_vel && state->joint_vel), "blf_fb_ik_integrate_hard: null state buffer");
+    BLF_REQUIRE(batch == 0 || state_given(state, kVel), "%s: null state buffer", fn);
     return launch_fb_ik(model, state, tasks, batch, steps, dT, nu, status, (hipStream_t)stream, slots, tau);
 }
 

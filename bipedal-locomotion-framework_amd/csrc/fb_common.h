@@ -587,5 +587,24 @@ Model to_model(const blf_fb_model* md)
     return m;
 }
 
+// The launch of every per-system kernel (see Half): while a system fits half a wavefront, n + 6 <= 32,
+// kernel k2 with a block per two systems, each with lds2 bytes of LDS; otherwise k1 with a block and
+// lds1 bytes per system.  Both kernels take the same arguments.  An empty batch launches nothing.
+constexpr int kNW = BLF_FBD_MAX_DOFS + 6;   // the rows (NVMAX) of the one-system-per-wavefront instantiations
+inline size_t fb_launch_lds(int n, size_t lds2, size_t lds1) { return n + 6 <= 32 ? 2 * lds2 : lds1; }
+
+template <class... P, class... A>
+blf_status fb_launch(const char* what, void (*k2)(P...), size_t lds2, void (*k1)(P...), size_t lds1, int n,
+                     int64_t batch, hipStream_t s, const A&... args)
+{
+    if (batch == 0) return BLF_OK;
+    const size_t lds = fb_launch_lds(n, lds2, lds1);
+    if (n + 6 <= 32)
+        hipLaunchKernelGGL(k2, dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), lds, s, args...);
+    else
+        hipLaunchKernelGGL(k1, dim3((unsigned)batch), dim3(kWave), lds, s, args...);
+    return check_hip(hipGetLastError(), what);
+}
+
 }  // namespace
 }  // namespace blf

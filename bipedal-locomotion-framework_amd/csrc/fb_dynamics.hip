@@ -1588,24 +1588,22 @@ static bool use_aba(const double* reg)
     return on && reg == nullptr;
 }
 
+// The launchers below hand fb_launch (fb_common.h) the two layouts' kernels: NV = HW = 32 for two systems
+// per wavefront, NV = kNW and HW = kWave for one.  FBD_KERNEL: kernel K's instantiation for the
+// launcher's `pri` (the model has prismatic joints) and `aba`.
+#define FBD_KERNEL(K, NV, HW) (pri ? (aba ? K<NV, HW, true, true> : K<NV, HW, true, false>) \
+                                   : (aba ? K<NV, HW, false, true> : K<NV, HW, false, false>))
+
 blf_status launch_fbd_dynamics(const blf_fb_model* md, const blf_fb_state* st, const double* tau,
                                const blf_fb_contacts* ct, const double* reg, int64_t batch,
                                const blf_fb_state* out, hipStream_t s)
 {
-    if (batch == 0) return BLF_OK;
     const Contacts c = to_contacts(ct);
     const bool pri = md->joint_type != nullptr, aba = use_aba(reg);
     const size_t lds = fbd_lds_bytes(md->ndof, c.C, aba);
-#define FBD_DYN(NV, HW) (pri ? (aba ? fbd_dynamics_kernel<NV, HW, true, true> : fbd_dynamics_kernel<NV, HW, true, false>) \
-                             : (aba ? fbd_dynamics_kernel<NV, HW, false, true> : fbd_dynamics_kernel<NV, HW, false, false>))
-    if (md->ndof + 6 <= 32)   // two systems per wavefront
-        hipLaunchKernelGGL(FBD_DYN(32, 32), dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds, s,
-                           to_model(md), *st, tau, c, reg, *out, batch);
-    else
-        hipLaunchKernelGGL(FBD_DYN(BLF_FBD_MAX_DOFS + 6, kWave), dim3((unsigned)batch), dim3(kWave), lds, s,
-                           to_model(md), *st, tau, c, reg, *out, batch);
-#undef FBD_DYN
-    return check_hip(hipGetLastError(), "fbd_dynamics_kernel launch");
+    return fb_launch("fbd_dynamics_kernel launch", FBD_KERNEL(fbd_dynamics_kernel, 32, 32), lds,
+                     FBD_KERNEL(fbd_dynamics_kernel, kNW, kWave), lds, md->ndof, batch, s, to_model(md), *st, tau, c,
+                     reg, *out, batch);
 }
 
 blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, const double* tau,
@@ -1613,29 +1611,20 @@ blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, cons
                             int32_t nsteps, double dT, double dT_last, hipStream_t s,
                             const blf_joint_impedance* impedance)
 {
-    if (batch == 0) return BLF_OK;
     const Contacts c = to_contacts(ct);
     Impedance imp{nullptr, nullptr, nullptr};
     if (impedance) imp = Impedance{impedance->kp, impedance->kd, impedance->q_ref};
     const bool pri = md->joint_type != nullptr, aba = use_aba(reg);
     const size_t lds = fbd_lds_bytes(md->ndof, c.C, aba);
-#define FBD_EUL(NV, HW) (pri ? (aba ? fbd_euler_kernel<NV, HW, true, true> : fbd_euler_kernel<NV, HW, true, false>) \
-                             : (aba ? fbd_euler_kernel<NV, HW, false, true> : fbd_euler_kernel<NV, HW, false, false>))
-    if (md->ndof + 6 <= 32)   // two systems per wavefront
-        hipLaunchKernelGGL(FBD_EUL(32, 32), dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds, s,
-                           to_model(md), *st, tau, c, reg, nsteps, dT, dT_last, imp, batch);
-    else
-        hipLaunchKernelGGL(FBD_EUL(BLF_FBD_MAX_DOFS + 6, kWave), dim3((unsigned)batch), dim3(kWave), lds, s,
-                           to_model(md), *st, tau, c, reg, nsteps, dT, dT_last, imp, batch);
-#undef FBD_EUL
-    return check_hip(hipGetLastError(), "fbd_euler_kernel launch");
+    return fb_launch("fbd_euler_kernel launch", FBD_KERNEL(fbd_euler_kernel, 32, 32), lds,
+                     FBD_KERNEL(fbd_euler_kernel, kNW, kWave), lds, md->ndof, batch, s, to_model(md), *st, tau, c, reg,
+                     nsteps, dT, dT_last, imp, batch);
 }
 
 blf_status launch_fbd_euler_traj(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
                                  const double* reg, int64_t batch, int32_t nsteps, double dT, double dT_last,
                                  hipStream_t s, const blf_joint_impedance_traj* it)
 {
-    if (batch == 0) return BLF_OK;
     const Contacts c = to_contacts(ct);
     const ImpedanceTraj imp{it->kp, it->kd, it->q_ref, it->qd_ref, it->q_bias, it->qd_stride, it->slices,
                             it->steps_per_slice};
@@ -1643,57 +1632,36 @@ blf_status launch_fbd_euler_traj(const blf_fb_model* md, const blf_fb_state* st,
     const size_t lds = fbd_lds_bytes(md->ndof, c.C, aba);
     // two systems per wavefront: the slice's qdref behind each system's block (the kernel's nx)
     const size_t ext = sizeof(double) * (size_t)((md->ndof + 1) & ~1);
-#define FBD_TRJ(NV, HW) (pri ? (aba ? fbd_euler_traj_kernel<NV, HW, true, true> : fbd_euler_traj_kernel<NV, HW, true, false>) \
-                             : (aba ? fbd_euler_traj_kernel<NV, HW, false, true> : fbd_euler_traj_kernel<NV, HW, false, false>))
-    if (md->ndof + 6 <= 32)
-        hipLaunchKernelGGL(FBD_TRJ(32, 32), dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * (lds + ext), s,
-                           to_model(md), *st, c, reg, nsteps, dT, dT_last, imp, batch);
-    else
-        hipLaunchKernelGGL(FBD_TRJ(BLF_FBD_MAX_DOFS + 6, kWave), dim3((unsigned)batch), dim3(kWave), lds, s,
-                           to_model(md), *st, c, reg, nsteps, dT, dT_last, imp, batch);
-#undef FBD_TRJ
-    return check_hip(hipGetLastError(), "fbd_euler_traj_kernel launch");
+    return fb_launch("fbd_euler_traj_kernel launch", FBD_KERNEL(fbd_euler_traj_kernel, 32, 32), lds + ext,
+                     FBD_KERNEL(fbd_euler_traj_kernel, kNW, kWave), lds, md->ndof, batch, s, to_model(md), *st, c, reg,
+                     nsteps, dT, dT_last, imp, batch);
 }
 
 blf_status launch_fb_invdyn(const blf_fb_model* md, const blf_fb_state* st, const double* joint_acc,
                             const double* base_acc, const blf_fb_contacts* ct, int64_t batch, double* tau,
                             double* bout, int32_t* status, hipStream_t s)
 {
-    if (batch == 0) return BLF_OK;
     const Contacts c = to_contacts(ct);
     const bool pri = md->joint_type != nullptr;
     const size_t lds = fbd_lds_bytes(md->ndof, c.C, true);
-    if (md->ndof + 6 <= 32)   // two systems per wavefront
-        hipLaunchKernelGGL((pri ? fb_invdyn_kernel<32, true> : fb_invdyn_kernel<32, false>),
-                           dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds, s, to_model(md), *st, joint_acc,
-                           base_acc, c, tau, bout, status, batch);
-    else
-        hipLaunchKernelGGL((pri ? fb_invdyn_kernel<kWave, true> : fb_invdyn_kernel<kWave, false>),
-                           dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, joint_acc, base_acc, c, tau,
-                           bout, status, batch);
-    return check_hip(hipGetLastError(), "fb_invdyn_kernel launch");
+    return fb_launch("fb_invdyn_kernel launch", pri ? fb_invdyn_kernel<32, true> : fb_invdyn_kernel<32, false>, lds,
+                     pri ? fb_invdyn_kernel<kWave, true> : fb_invdyn_kernel<kWave, false>, lds, md->ndof, batch, s,
+                     to_model(md), *st, joint_acc, base_acc, c, tau, bout, status, batch);
 }
 
 blf_status launch_fbd_euler_ctq(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
                                 int64_t batch, int32_t nsteps, double dT, double dT_last, hipStream_t s,
                                 const blf_computed_torque_traj* it)
 {
-    if (batch == 0) return BLF_OK;
     const Contacts c = to_contacts(ct);
     const ComputedTorqueTraj law{it->kp, it->kd, it->q_ref, it->qd_ref, it->qdd_ref, it->q_bias, it->tau_max,
                                  it->tau_last, it->qd_stride, it->qdd_stride, it->slices, it->steps_per_slice};
     const bool pri = md->joint_type != nullptr;
     const size_t lds = fbd_lds_bytes(md->ndof, c.C, true);
-    if (md->ndof + 6 <= 32)
-        hipLaunchKernelGGL((pri ? fbd_euler_ctq_kernel<32, 32, true, true> : fbd_euler_ctq_kernel<32, 32, false, true>),
-                           dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), 2 * lds, s, to_model(md), *st, c, nsteps,
-                           dT, dT_last, law, batch);
-    else
-        hipLaunchKernelGGL((pri ? fbd_euler_ctq_kernel<BLF_FBD_MAX_DOFS + 6, kWave, true, true>
-                                : fbd_euler_ctq_kernel<BLF_FBD_MAX_DOFS + 6, kWave, false, true>),
-                           dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, c, nsteps, dT, dT_last, law,
-                           batch);
-    return check_hip(hipGetLastError(), "fbd_euler_ctq_kernel launch");
+    return fb_launch("fbd_euler_ctq_kernel launch",
+                     pri ? fbd_euler_ctq_kernel<32, 32, true, true> : fbd_euler_ctq_kernel<32, 32, false, true>, lds,
+                     pri ? fbd_euler_ctq_kernel<kNW, kWave, true, true> : fbd_euler_ctq_kernel<kNW, kWave, false, true>,
+                     lds, md->ndof, batch, s, to_model(md), *st, c, nsteps, dT, dT_last, law, batch);
 }
 
 blf_status launch_com_reference(const double* xi0, const double* vrp, int64_t vstride, const double* omega0,

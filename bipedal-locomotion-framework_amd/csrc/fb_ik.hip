@@ -1505,16 +1505,22 @@ __global__ __launch_bounds__(64) void fb_ik_kernel(Model m, blf_fb_state st, IkT
 // Two robots per wavefront while a robot's rows fit half of one (n + 6 <= 32), as the dynamics
 // kernels: at n = 24, B = 16 384 the solve takes 0.431 ms with two robots per wavefront and 0.965 ms
 // with one, and 20 fused steps 6.29 against 15.24 ms (profiles/ik_bench.log).
+// a robot's LDS bytes in the layout of nvmax rows (32: two robots per wavefront, kNW: one)
+static size_t ik_lds(int n, int K, int nvmax, bool limits)
+{
+    return sizeof(double) * IkSmem(nullptr, n, K, nvmax, limits).total;
+}
+
+static size_t ik_track_lds(int n, int K, int nvmax) { return sizeof(double) * IkTrackSmem(nullptr, n, K, nvmax).total; }
+
 size_t fb_ik_lds_bytes(int n, int K, bool limits)
 {
-    return n + 6 <= 32 ? 2 * sizeof(double) * IkSmem(nullptr, n, K, 32, limits).total
-                       : sizeof(double) * IkSmem(nullptr, n, K, BLF_FBD_MAX_DOFS + 6, limits).total;
+    return fb_launch_lds(n, ik_lds(n, K, 32, limits), ik_lds(n, K, kNW, limits));
 }
 
 size_t fb_ik_track_lds_bytes(int n, int K)
 {
-    return n + 6 <= 32 ? 2 * sizeof(double) * IkTrackSmem(nullptr, n, K, 32).total
-                       : sizeof(double) * IkTrackSmem(nullptr, n, K, BLF_FBD_MAX_DOFS + 6).total;
+    return fb_launch_lds(n, ik_track_lds(n, K, 32), ik_track_lds(n, K, kNW));
 }
 
 static IkTasks to_tasks(const blf_ik_tasks* t)
@@ -1543,24 +1549,23 @@ blf_status launch_fb_ik(const blf_fb_model* md, const blf_fb_state* st, const bl
                         int32_t steps, double dT, double* nu, int32_t* status, hipStream_t s,
                         uint32_t slots, double tau)
 {
-    if (batch == 0) return BLF_OK;
     const IkTasks tk = to_tasks(t);
     const bool pri = md->joint_type != nullptr;
-    const size_t lds = fb_ik_lds_bytes(md->ndof, tk.K);
+    const int n = md->ndof;
     const IkHard hd{slots, tau};
-    constexpr int NW = BLF_FBD_MAX_DOFS + 6;
-    if (md->ndof + 6 <= 32) {
-        auto kern = slots ? (pri ? fb_ik_kernel<32, 32, true, true> : fb_ik_kernel<32, 32, false, true>)
-                          : (pri ? fb_ik_kernel<32, 32, true, false> : fb_ik_kernel<32, 32, false, false>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), lds, s, to_model(md), *st, tk,
-                           steps, dT, nu, status, batch, hd);
-    } else {
-        auto kern = slots ? (pri ? fb_ik_kernel<NW, kWave, true, true> : fb_ik_kernel<NW, kWave, false, true>)
-                          : (pri ? fb_ik_kernel<NW, kWave, true, false> : fb_ik_kernel<NW, kWave, false, false>);
-        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, tk, steps, dT, nu,
-                           status, batch, hd);
-    }
-    return check_hip(hipGetLastError(), "fb_ik_kernel launch");
+    auto k2 = slots ? (pri ? fb_ik_kernel<32, 32, true, true> : fb_ik_kernel<32, 32, false, true>)
+                    : (pri ? fb_ik_kernel<32, 32, true, false> : fb_ik_kernel<32, 32, false, false>);
+    auto k1 = slots ? (pri ? fb_ik_kernel<kNW, kWave, true, true> : fb_ik_kernel<kNW, kWave, false, true>)
+                    : (pri ? fb_ik_kernel<kNW, kWave, true, false> : fb_ik_kernel<kNW, kWave, false, false>);
+    return fb_launch("fb_ik_kernel launch", k2, ik_lds(n, tk.K, 32, false), k1, ik_lds(n, tk.K, kNW, false), n, batch,
+                     s, to_model(md), *st, tk, steps, dT, nu, status, batch, hd);
+}
+
+// blf_ik_limits as the kernels take it; null: no box
+static IkLimits to_limits(const blf_ik_limits* lim)
+{
+    if (lim == nullptr) return IkLimits{nullptr, nullptr, nullptr, nullptr, 1.0, BLF_IK_LIMITS_DEFAULT_MAX_ITER};
+    return IkLimits{lim->pos_lower, lim->pos_upper, lim->klim, lim->vel_max, lim->sampling_time, lim->max_iter};
 }
 
 blf_status launch_fb_ik_limits(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t,
@@ -1568,24 +1573,17 @@ blf_status launch_fb_ik_limits(const blf_fb_model* md, const blf_fb_state* st, c
                                int32_t* status, int32_t* iters, uint64_t* active, hipStream_t s, uint32_t slots,
                                double tau)
 {
-    if (batch == 0) return BLF_OK;
     const IkTasks tk = to_tasks(t);
     const bool pri = md->joint_type != nullptr;
-    const size_t lds = fb_ik_lds_bytes(md->ndof, tk.K, true);
+    const int n = md->ndof;
     const IkHard hd{slots, tau};
-    const IkLimits lp{lim->pos_lower, lim->pos_upper, lim->klim, lim->vel_max, lim->sampling_time, lim->max_iter};
     unsigned long long* act = reinterpret_cast<unsigned long long*>(active);
-    constexpr int NW = BLF_FBD_MAX_DOFS + 6;
-    if (md->ndof + 6 <= 32) {
-        auto kern = pri ? fb_ik_limits_kernel<32, 32, true> : fb_ik_limits_kernel<32, 32, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), lds, s, to_model(md), *st, tk,
-                           steps, dT, nu, status, batch, hd, lp, iters, act);
-    } else {
-        auto kern = pri ? fb_ik_limits_kernel<NW, kWave, true> : fb_ik_limits_kernel<NW, kWave, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, tk, steps, dT, nu,
-                           status, batch, hd, lp, iters, act);
-    }
-    return check_hip(hipGetLastError(), "fb_ik_limits_kernel launch");
+    return fb_launch("fb_ik_limits_kernel launch",
+                     pri ? fb_ik_limits_kernel<32, 32, true> : fb_ik_limits_kernel<32, 32, false>,
+                     ik_lds(n, tk.K, 32, true),
+                     pri ? fb_ik_limits_kernel<kNW, kWave, true> : fb_ik_limits_kernel<kNW, kWave, false>,
+                     ik_lds(n, tk.K, kNW, true), n, batch, s, to_model(md), *st, tk, steps, dT, nu, status, batch, hd,
+                     to_limits(lim), iters, act);
 }
 
 blf_status launch_fb_ik_track(const blf_fb_model* md, const blf_fb_state* st, const blf_ik_tasks* t,
@@ -1594,27 +1592,18 @@ blf_status launch_fb_ik_track(const blf_fb_model* md, const blf_fb_state* st, co
                               int32_t* fail_step, int32_t* iters, uint64_t* active, hipStream_t s, uint32_t base,
                               uint32_t stance, double tau)
 {
-    if (batch == 0) return BLF_OK;
     const IkTasks tk = to_tasks(t);
     const bool pri = md->joint_type != nullptr;
-    const size_t lds = fb_ik_track_lds_bytes(md->ndof, tk.K);
-    const IkLimits lp = lim ? IkLimits{lim->pos_lower, lim->pos_upper, lim->klim, lim->vel_max, lim->sampling_time,
-                                       lim->max_iter}
-                            : IkLimits{nullptr, nullptr, nullptr, nullptr, 1.0, BLF_IK_LIMITS_DEFAULT_MAX_ITER};
+    const int n = md->ndof;
     const IkTrack tr{sch->steps, base, stance, sch->contact, sch->se3_pose, sch->se3_twist, sch->com_pos,
                      sch->com_vel, joint_traj, base_traj, nu_traj, fail_step};
     unsigned long long* act = reinterpret_cast<unsigned long long*>(active);
-    constexpr int NW = BLF_FBD_MAX_DOFS + 6;
-    if (md->ndof + 6 <= 32) {
-        auto kern = pri ? fb_ik_track_kernel<32, 32, true> : fb_ik_track_kernel<32, 32, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div(batch, 2)), dim3(kWave), lds, s, to_model(md), *st, tk, tr,
-                           dT, status, batch, tau, lp, iters, act);
-    } else {
-        auto kern = pri ? fb_ik_track_kernel<NW, kWave, true> : fb_ik_track_kernel<NW, kWave, false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)batch), dim3(kWave), lds, s, to_model(md), *st, tk, tr, dT, status,
-                           batch, tau, lp, iters, act);
-    }
-    return check_hip(hipGetLastError(), "fb_ik_track_kernel launch");
+    return fb_launch("fb_ik_track_kernel launch",
+                     pri ? fb_ik_track_kernel<32, 32, true> : fb_ik_track_kernel<32, 32, false>,
+                     ik_track_lds(n, tk.K, 32),
+                     pri ? fb_ik_track_kernel<kNW, kWave, true> : fb_ik_track_kernel<kNW, kWave, false>,
+                     ik_track_lds(n, tk.K, kNW), n, batch, s, to_model(md), *st, tk, tr, dT, status, batch, tau,
+                     to_limits(lim), iters, act);
 }
 
 }  // namespace blf
