@@ -7,7 +7,7 @@
  *   ContinousContactModelTest.cpp:30-214 (device) and FloatingBaseSystemKinematics under
  *   ForwardEuler (device), and ParametersHandlerYarpTest.cpp:30-140 on the reference's own
  *   config.ini (tests/golden/parameters_config.ini) read by StdImplementation::setFromFile.
- * usage: blf_host_tests [cpu|gpu|all]   (exit status = number of failed checks)
+ * usage: blf_host_tests [cpu|gpu|all]   (output and exit status: test_harness.h)
  */
 #include <array>
 #include <cmath>
@@ -36,20 +36,11 @@
 #include <BipedalLocomotion/System/VariablesHandler.h>
 #include <blf/urdf.h>
 
+#include "test_harness.h"
+
 using namespace BipedalLocomotion;
 using namespace BipedalLocomotion::Planners;
 using namespace BipedalLocomotion::System;
-
-static int g_failed = 0, g_checks = 0;
-#define REQUIRE(cond)                                                                          \
-    do {                                                                                       \
-        ++g_checks;                                                                            \
-        if (!(cond)) {                                                                         \
-            ++g_failed;                                                                        \
-            std::fprintf(stderr, "  FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
-        }                                                                                      \
-    } while (0)
-#define REQUIRE_FALSE(cond) REQUIRE(!(cond))
 
 static bool sameContact(const Contact& a, const Contact& b)
 {
@@ -1524,13 +1515,9 @@ static int dumpUrdf(int argc, char** argv)
 
 int main(int argc, char** argv)
 {
-    const std::string which = argc > 1 ? argv[1] : "all";
-    if (which == "urdf") return dumpUrdf(argc, argv);
+    if (argc > 1 && std::strcmp(argv[1], "urdf") == 0) return dumpUrdf(argc, argv);
     if (const char* g = std::getenv("BLF_GOLDEN_DIR")) g_golden = g;
-    const bool cpu = which == "cpu" || which == "all";
-    const bool gpu = which == "gpu" || which == "all";
-    struct T { const char* name; bool device; std::function<void()> fn; };
-    const std::vector<T> tests = {
+    return runCases(argc, argv, {
         {"ContactList", false, testContactList},
         {"ContactPhaseList", false, testContactPhaseList},
         {"VariablesHandler", false, testVariablesHandler},
@@ -1552,14 +1539,5 @@ int main(int argc, char** argv)
         {"FloatingBaseDynamicalSystem, any ContactModel", true, testFloatingBaseDynamicsAnyContactModel},
         {"Fixed joints (model merge)", false, testFixedJoints},
         {"Fixed / prismatic joints (device)", true, testFixedJointsDevice},
-    };
-    for (const auto& t : tests)
-    {
-        if ((t.device && !gpu) || (!t.device && !cpu)) continue;
-        const int before = g_failed;
-        t.fn();
-        std::printf("%-32s %s\n", t.name, g_failed == before ? "ok" : "FAILED");
-    }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed;
+    });
 }

@@ -22,52 +22,12 @@
 #include <BipedalLocomotion/ParametersHandler/IParametersHandler.h>
 #include <blf/urdf.h>
 
+#include "ik_fixtures.h"
+#include "test_harness.h"
+
 using namespace BipedalLocomotion;
 using namespace BipedalLocomotion::IK;
 using namespace BipedalLocomotion::ParametersHandler;
-
-static int g_failed = 0, g_checks = 0;
-#define REQUIRE(cond)                                                                          \
-    do {                                                                                       \
-        ++g_checks;                                                                            \
-        if (!(cond)) {                                                                         \
-            ++g_failed;                                                                        \
-            std::fprintf(stderr, "  FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
-        }                                                                                      \
-    } while (0)
-#define REQUIRE_FALSE(cond) REQUIRE(!(cond))
-
-static constexpr int kJoints = 13;
-
-static std::shared_ptr<SE3Task> se3Task(int frame)
-{
-    auto h = std::make_shared<StdImplementation>();
-    h->setParameter("frame_index", frame);
-    h->setParameter("kp_linear", 4.0);
-    h->setParameter("kp_angular", 3.0);
-    auto t = std::make_shared<SE3Task>();
-    t->initialize(h);
-    return t;
-}
-
-static std::shared_ptr<CoMTask> comTask()
-{
-    auto h = std::make_shared<StdImplementation>();
-    h->setParameter("kp_linear", 2.0);
-    auto t = std::make_shared<CoMTask>();
-    t->initialize(h);
-    return t;
-}
-
-static std::shared_ptr<JointTrackingTask> jointTask()
-{
-    auto h = std::make_shared<StdImplementation>();
-    h->setParameter("kp", std::vector<double>(kJoints, 1.5));
-    auto t = std::make_shared<JointTrackingTask>();
-    t->initialize(h);
-    return t;
-}
-
 
 static std::shared_ptr<StdImplementation> limitsHandler(int n = kJoints, double velocity = 0.0)
 {
@@ -226,35 +186,6 @@ static int dumpUrdfLimits(const char* path)
 }
 
 // ---- device cases ----------------------------------------------------------------------------------
-// pelvis, two legs of six joints (hip yaw / roll / pitch, knee, ankle pitch / roll), one torso joint;
-// sole frames on the feet.  (ik_tests.cpp's biped has three joints per leg: with both soles planted it
-// is a closed chain with a redundant constraint, so its twelve foot rows are dependent.)
-static blf::RobotModel bipedModel()
-{
-    blf::RobotModel m;
-    m.ndof = kJoints;
-    m.parent = {0, 1, 2, 3, 4, 5, 0, 7, 8, 9, 10, 11, 0};
-    for (double side : {0.08, -0.08})
-        m.jointOrigin.insert(m.jointOrigin.end(), {0.0, side, -0.05, 0.0, 0.0, -0.02, 0.0, 0.0, -0.02,
-                                                   0.0, 0.0, -0.25, 0.0, 0.0, -0.25, 0.0, 0.0, -0.02});
-    m.jointOrigin.insert(m.jointOrigin.end(), {0.0, 0.0, 0.1});
-    for (int j = 0; j < kJoints; ++j) m.jointRotation.insert(m.jointRotation.end(), {1, 0, 0, 0, 1, 0, 0, 0, 1});
-    for (int leg = 0; leg < 2; ++leg)
-        m.jointAxis.insert(m.jointAxis.end(), {0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 1, 0, 0});
-    m.jointAxis.insert(m.jointAxis.end(), {0, 0, 1});
-    m.linkMass = {6.0, 1.0, 0.5, 2.0, 1.5, 0.3, 0.8, 1.0, 0.5, 2.0, 1.5, 0.3, 0.8, 5.0};
-    m.linkCom = {0.0, 0.0, 0.02};
-    for (int leg = 0; leg < 2; ++leg)
-        m.linkCom.insert(m.linkCom.end(), {0.0, 0.0, -0.01, 0.0, 0.0, -0.01, 0.0, 0.0, -0.12,
-                                           0.0, 0.0, -0.12, 0.0, 0.0, -0.01, 0.03, 0.0, -0.02});
-    m.linkCom.insert(m.linkCom.end(), {0.0, 0.0, 0.15});
-    for (double mass : m.linkMass)
-        m.linkInertia.insert(m.linkInertia.end(), {0.01 * mass, 0, 0, 0, 0.012 * mass, 0, 0, 0, 0.008 * mass});
-    m.frameLink = {6, 12};
-    m.framePose = {0.02, 0.0, -0.04, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0.02, 0.0, -0.04, 1, 0, 0, 0, 1, 0, 0, 0, 1};
-    return m;
-}
-
 static const blf::Vector3 kBase0{{0.01, -0.02, 0.6}};
 static blf::VectorXd joints0()
 {
@@ -385,26 +316,13 @@ static void testInfeasibleLimitsOnDevice()
 
 int main(int argc, char** argv)
 {
-    const std::string which = argc > 1 ? argv[1] : "all";
-    if (which == "urdf" && argc > 2) return dumpUrdfLimits(argv[2]);
-    const bool cpu = which == "cpu" || which == "all";
-    const bool gpu = which == "gpu" || which == "all";
-    struct T { const char* name; bool device; std::function<void()> fn; };
-    const std::vector<T> tests = {
+    if (argc > 2 && std::strcmp(argv[1], "urdf") == 0) return dumpUrdfLimits(argv[2]);
+    return runCases(argc, argv, {
         {"JointLimitsTask keys", false, testLimitsTaskKeys},
         {"QPInverseKinematics limits task bookkeeping", false, testLimitsTaskBookkeeping},
         {"loadUrdf joint limits", false, testUrdfLimits},
         {"QPInverseKinematics limits finalize", true, testFinalizeRefusals},
         {"QPInverseKinematics limits on the device", true, testLimitsOnDevice},
         {"QPInverseKinematics infeasible limits", true, testInfeasibleLimitsOnDevice},
-    };
-    for (const auto& t : tests)
-    {
-        if ((t.device && !gpu) || (!t.device && !cpu)) continue;
-        const int before = g_failed;
-        t.fn();
-        std::printf("%-44s %s\n", t.name, g_failed == before ? "ok" : "FAILED");
-    }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed;
+    });
 }

@@ -23,51 +23,12 @@
 #include <BipedalLocomotion/IK/QPInverseKinematics.h>
 #include <BipedalLocomotion/ParametersHandler/IParametersHandler.h>
 
+#include "ik_fixtures.h"
+#include "test_harness.h"
+
 using namespace BipedalLocomotion;
 using namespace BipedalLocomotion::IK;
 using namespace BipedalLocomotion::ParametersHandler;
-
-static int g_failed = 0, g_checks = 0;
-#define REQUIRE(cond)                                                                          \
-    do {                                                                                       \
-        ++g_checks;                                                                            \
-        if (!(cond)) {                                                                         \
-            ++g_failed;                                                                        \
-            std::fprintf(stderr, "  FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
-        }                                                                                      \
-    } while (0)
-#define REQUIRE_FALSE(cond) REQUIRE(!(cond))
-
-static constexpr int kJoints = 13;
-
-static std::shared_ptr<SE3Task> se3Task(int frame)
-{
-    auto h = std::make_shared<StdImplementation>();
-    h->setParameter("frame_index", frame);
-    h->setParameter("kp_linear", 4.0);
-    h->setParameter("kp_angular", 3.0);
-    auto t = std::make_shared<SE3Task>();
-    t->initialize(h);
-    return t;
-}
-
-static std::shared_ptr<CoMTask> comTask()
-{
-    auto h = std::make_shared<StdImplementation>();
-    h->setParameter("kp_linear", 2.0);
-    auto t = std::make_shared<CoMTask>();
-    t->initialize(h);
-    return t;
-}
-
-static std::shared_ptr<JointTrackingTask> jointTask()
-{
-    auto h = std::make_shared<StdImplementation>();
-    h->setParameter("kp", std::vector<double>(kJoints, 1.5));
-    auto t = std::make_shared<JointTrackingTask>();
-    t->initialize(h);
-    return t;
-}
 
 static std::shared_ptr<JointLimitsTask> limitsTask()
 {
@@ -123,32 +84,6 @@ static void testPriorityBookkeeping()
     REQUIRE_FALSE(ik.setTaskPriority("hand", 0));     // a zero weight
     REQUIRE(ik.hardRows() == pinned);
     REQUIRE(ik.getTaskNames().size() == 7);
-}
-
-static blf::RobotModel bipedModel()
-{
-    blf::RobotModel m;
-    m.ndof = kJoints;
-    m.parent = {0, 1, 2, 3, 4, 5, 0, 7, 8, 9, 10, 11, 0};
-    for (double side : {0.08, -0.08})
-        m.jointOrigin.insert(m.jointOrigin.end(), {0.0, side, -0.05, 0.0, 0.0, -0.02, 0.0, 0.0, -0.02,
-                                                   0.0, 0.0, -0.25, 0.0, 0.0, -0.25, 0.0, 0.0, -0.02});
-    m.jointOrigin.insert(m.jointOrigin.end(), {0.0, 0.0, 0.1});
-    for (int j = 0; j < kJoints; ++j) m.jointRotation.insert(m.jointRotation.end(), {1, 0, 0, 0, 1, 0, 0, 0, 1});
-    for (int leg = 0; leg < 2; ++leg)
-        m.jointAxis.insert(m.jointAxis.end(), {0, 0, 1, 1, 0, 0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 1, 0, 0});
-    m.jointAxis.insert(m.jointAxis.end(), {0, 0, 1});
-    m.linkMass = {6.0, 1.0, 0.5, 2.0, 1.5, 0.3, 0.8, 1.0, 0.5, 2.0, 1.5, 0.3, 0.8, 5.0};
-    m.linkCom = {0.0, 0.0, 0.02};
-    for (int leg = 0; leg < 2; ++leg)
-        m.linkCom.insert(m.linkCom.end(), {0.0, 0.0, -0.01, 0.0, 0.0, -0.01, 0.0, 0.0, -0.12,
-                                           0.0, 0.0, -0.12, 0.0, 0.0, -0.01, 0.03, 0.0, -0.02});
-    m.linkCom.insert(m.linkCom.end(), {0.0, 0.0, 0.15});
-    for (double mass : m.linkMass)
-        m.linkInertia.insert(m.linkInertia.end(), {0.01 * mass, 0, 0, 0, 0.012 * mass, 0, 0, 0, 0.008 * mass});
-    m.frameLink = {6, 12};
-    m.framePose = {0.02, 0.0, -0.04, 1, 0, 0, 0, 1, 0, 0, 0, 1, 0.02, 0.0, -0.04, 1, 0, 0, 0, 1, 0, 0, 0, 1};
-    return m;
 }
 
 struct Biped
@@ -240,21 +175,8 @@ static void testPriorityOnDevice()
 
 int main(int argc, char** argv)
 {
-    const std::string which = argc > 1 ? argv[1] : "all";
-    const bool cpu = which == "cpu" || which == "all";
-    const bool gpu = which == "gpu" || which == "all";
-    struct T { const char* name; bool device; std::function<void()> fn; };
-    const std::vector<T> tests = {
+    return runCases(argc, argv, {
         {"QPInverseKinematics task priority bookkeeping", false, testPriorityBookkeeping},
         {"QPInverseKinematics task priority on the device", true, testPriorityOnDevice},
-    };
-    for (const auto& t : tests)
-    {
-        if ((t.device && !gpu) || (!t.device && !cpu)) continue;
-        const int before = g_failed;
-        t.fn();
-        std::printf("%-48s %s\n", t.name, g_failed == before ? "ok" : "FAILED");
-    }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed;
+    });
 }

@@ -25,20 +25,11 @@
 #include <BipedalLocomotion/System/FloatingBaseSystemKinematics.h>
 #include <BipedalLocomotion/System/ForwardEuler.h>
 
+#include "test_harness.h"
+
 using namespace BipedalLocomotion;
 using namespace BipedalLocomotion::IK;
 using namespace BipedalLocomotion::ParametersHandler;
-
-static int g_failed = 0, g_checks = 0;
-#define REQUIRE(cond)                                                                          \
-    do {                                                                                       \
-        ++g_checks;                                                                            \
-        if (!(cond)) {                                                                         \
-            ++g_failed;                                                                        \
-            std::fprintf(stderr, "  FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
-        }                                                                                      \
-    } while (0)
-#define REQUIRE_FALSE(cond) REQUIRE(!(cond))
 
 static constexpr int kJoints = 7;
 
@@ -397,23 +388,10 @@ static void testIntegrationLoopOnDevice()
 
 int main(int argc, char** argv)
 {
-    const std::string which = argc > 1 ? argv[1] : "all";
-    const bool cpu = which == "cpu" || which == "all";
-    const bool gpu = which == "gpu" || which == "all";
-    struct T { const char* name; bool device; std::function<void()> fn; };
-    const std::vector<T> tests = {
+    return runCases(argc, argv, {
         {"IK tasks parameter handler", false, testTaskParameters},
         {"QPInverseKinematics task bookkeeping", false, testTaskBookkeeping},
         {"QPInverseKinematics on the device", true, testAdvanceOnDevice},
         {"IntegrationBasedIK loop on the device", true, testIntegrationLoopOnDevice},
-    };
-    for (const auto& t : tests)
-    {
-        if ((t.device && !gpu) || (!t.device && !cpu)) continue;
-        const int before = g_failed;
-        t.fn();
-        std::printf("%-40s %s\n", t.name, g_failed == before ? "ok" : "FAILED");
-    }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed;
+    });
 }

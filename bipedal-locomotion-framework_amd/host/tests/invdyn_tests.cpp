@@ -21,19 +21,10 @@
 #include <BipedalLocomotion/ParametersHandler/IParametersHandler.h>
 #include <BipedalLocomotion/System/FloatingBaseSystemDynamics.h>
 
+#include "test_harness.h"
+
 using namespace BipedalLocomotion;
 using namespace BipedalLocomotion::System;
-
-static int g_failed = 0, g_checks = 0;
-#define REQUIRE(cond)                                                                          \
-    do {                                                                                       \
-        ++g_checks;                                                                            \
-        if (!(cond)) {                                                                         \
-            ++g_failed;                                                                        \
-            std::fprintf(stderr, "  FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
-        }                                                                                      \
-    } while (0)
-#define REQUIRE_FALSE(cond) REQUIRE(!(cond))
 
 // host_tests.cpp's chain
 static blf::RobotModel chainModel()
@@ -118,21 +109,8 @@ static void testRoundTripOnDevice()
 
 int main(int argc, char** argv)
 {
-    const std::string which = argc > 1 ? argv[1] : "all";
-    const bool cpu = which == "cpu" || which == "all";
-    const bool gpu = which == "gpu" || which == "all";
-    struct T { const char* name; bool device; std::function<void()> fn; };
-    const std::vector<T> tests = {
+    return runCases(argc, argv, {
         {"FloatingBaseDynamicalSystem inverseDynamics refusals", false, testRefusedWithoutModel},
         {"FloatingBaseDynamicalSystem inverseDynamics on the device", true, testRoundTripOnDevice},
-    };
-    for (const auto& t : tests)
-    {
-        if ((t.device && !gpu) || (!t.device && !cpu)) continue;
-        const int before = g_failed;
-        t.fn();
-        std::printf("%-58s %s\n", t.name, g_failed == before ? "ok" : "FAILED");
-    }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed;
+    });
 }

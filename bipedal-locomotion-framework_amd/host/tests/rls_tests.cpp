@@ -20,19 +20,10 @@
 #include <BipedalLocomotion/Estimators/RecursiveLeastSquare.h>
 #include <BipedalLocomotion/ParametersHandler/IParametersHandler.h>
 
+#include "test_harness.h"
+
 using namespace BipedalLocomotion::Estimators;
 using namespace BipedalLocomotion::ParametersHandler;
-
-static int g_failed = 0, g_checks = 0;
-#define REQUIRE(cond)                                                                          \
-    do {                                                                                       \
-        ++g_checks;                                                                            \
-        if (!(cond)) {                                                                         \
-            ++g_failed;                                                                        \
-            std::fprintf(stderr, "  FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
-        }                                                                                      \
-    } while (0)
-#define REQUIRE_FALSE(cond) REQUIRE(!(cond))
 
 static std::string g_golden = "tests/golden";
 
@@ -182,23 +173,10 @@ static void testRecursiveLeastSquare()
 
 int main(int argc, char** argv)
 {
-    const std::string which = argc > 1 ? argv[1] : "all";
     if (const char* g = std::getenv("BLF_GOLDEN_DIR")) g_golden = g;
-    const bool cpu = which == "cpu" || which == "all";
-    const bool gpu = which == "gpu" || which == "all";
-    struct T { const char* name; bool device; std::function<void()> fn; };
-    const std::vector<T> tests = {
+    return runCases(argc, argv, {
         {"RecursiveLeastSquare state machine", false, testStateMachine},
         {"RecursiveLeastSquare config.ini", false, testConfigFile},
         {"Recursive Least Square", true, testRecursiveLeastSquare},
-    };
-    for (const auto& t : tests)
-    {
-        if ((t.device && !gpu) || (!t.device && !cpu)) continue;
-        const int before = g_failed;
-        t.fn();
-        std::printf("%-36s %s\n", t.name, g_failed == before ? "ok" : "FAILED");
-    }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed;
+    });
 }

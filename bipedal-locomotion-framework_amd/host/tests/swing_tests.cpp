@@ -1,5 +1,5 @@
 /**
- * @file swing_foot_tests.cpp
+ * @file swing_tests.cpp
  * Tests of the Planners::SwingFootPlanner and Planners::SO3Planner adapters, with host_tests.cpp's
  * conventions ("name ... ok", "N checks, 0 failed"; modes cpu / gpu / all):
  *   cpu: every path on which the adapters return false without touching a device (parameter
@@ -20,19 +20,10 @@
 #include <BipedalLocomotion/Planners/SO3Planner.h>
 #include <BipedalLocomotion/Planners/SwingFootPlanner.h>
 
+#include "test_harness.h"
+
 using namespace BipedalLocomotion::Planners;
 using namespace BipedalLocomotion::ParametersHandler;
-
-static int g_failed = 0, g_checks = 0;
-#define REQUIRE(cond)                                                                          \
-    do {                                                                                       \
-        ++g_checks;                                                                            \
-        if (!(cond)) {                                                                         \
-            ++g_failed;                                                                        \
-            std::fprintf(stderr, "  FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);           \
-        }                                                                                      \
-    } while (0)
-#define REQUIRE_FALSE(cond) REQUIRE(!(cond))
 
 static const double kDT = 0.0625, kHeight = 0.05, kApex = 0.4, kVland = -0.02, kAland = 0.1;
 
@@ -245,23 +236,10 @@ static void testSO3PlannerOnDevice()
 
 int main(int argc, char** argv)
 {
-    const std::string which = argc > 1 ? argv[1] : "all";
-    const bool cpu = which == "cpu" || which == "all";
-    const bool gpu = which == "gpu" || which == "all";
-    struct T { const char* name; bool device; std::function<void()> fn; };
-    const std::vector<T> tests = {
+    return runCases(argc, argv, {
         {"SwingFootPlanner parameter handler", false, testParameterHandler},
         {"SwingFootPlanner state machine", false, testStateMachine},
         {"SwingFootPlanner on the device", true, testSwingFootPlannerOnDevice},
         {"SO3Planner on the device", true, testSO3PlannerOnDevice},
-    };
-    for (const auto& t : tests)
-    {
-        if ((t.device && !gpu) || (!t.device && !cpu)) continue;
-        const int before = g_failed;
-        t.fn();
-        std::printf("%-36s %s\n", t.name, g_failed == before ? "ok" : "FAILED");
-    }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed;
+    });
 }

@@ -225,7 +225,7 @@ def refined_solve(A, b, rounds=5):
 
 
 def rel_err(a, b):
-    """tests/test_gpu_fb_dynamics.py's metric."""
+    """tests/gpu_util.py's metric as a Python float (this module imports no torch, so not gpu_util)."""
     return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
 
 

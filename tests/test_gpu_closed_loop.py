@@ -21,17 +21,10 @@ import closed_loop as CL
 import fb_dynamics as F
 from blf import closed_loop as DL
 from blf import native, problems as P, robot as R
+from gpu_util import rel_err, to_device as _d
 
 pytestmark = pytest.mark.gpu
 MODEL = R.humanoid24()
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def rel_err(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def test_fb_dcm_vs_oracle(handle):

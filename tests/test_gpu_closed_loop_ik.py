@@ -9,13 +9,10 @@ import closed_loop_ik_reference as IR
 import ik_limits_reference as LR
 from blf import closed_loop as DL
 from blf import native, problems as P, robot as R
+from gpu_util import rel_err
 
 pytestmark = pytest.mark.gpu
 MODEL = R.humanoid24()
-
-
-def rel_err(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def _setup(B, periods, seed=3):

@@ -8,17 +8,10 @@ import torch
 
 import closed_loop_ik_reference as IR
 from blf import native
+from gpu_util import rel_err, to_device as _d
 
 pytestmark = pytest.mark.gpu
 N, K, COL = 5, 7, 3   # vrp [B][N][2] and omega [B][K] read at column COL: both strided
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def rel_err(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def inputs(B, seed=0):

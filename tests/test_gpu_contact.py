@@ -13,6 +13,7 @@ from blf import native
 pytestmark = pytest.mark.gpu
 
 
+# local: fp64 only, converted by numpy before torch.from_numpy
 def _d(a):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).cuda()
 

@@ -48,6 +48,7 @@ import torch
 import contact_exact as CE
 import rls_reference as R
 from blf import native, robot
+from gpu_util import to_device as _d
 
 pytestmark = pytest.mark.gpu
 
@@ -58,10 +59,6 @@ FX = {k: v for k, v in np.load(os.path.join(os.path.dirname(__file__), "golden",
                                             "contact_exact.npz")).items()}
 FAMILIES = [str(f) for f in FX["families"]]
 INPUTS = ("prm", "twist", "pose", "null")
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
 
 
 def _d_unaligned(a):

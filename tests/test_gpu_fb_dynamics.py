@@ -10,14 +10,11 @@ import torch
 
 import fb_dynamics as F
 from blf import native, robot
+from gpu_util import rel_err, to_device as _d
 
 pytestmark = pytest.mark.gpu
 MODEL = robot.humanoid24()
 TOL = 1e-9
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
 
 
 def contacts_for(B, seed=0):
@@ -29,10 +26,6 @@ def contacts_for(B, seed=0):
     host = dict(frame=np.array([0, 1], dtype=np.int32), params=params, null_pose=null)
     dev = dict(frame=_d(host["frame"], torch.int32), params=_d(params), null_pose=_d(null))
     return host, dev
-
-
-def rel_err(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 @pytest.mark.parametrize("with_contacts", [False, True])

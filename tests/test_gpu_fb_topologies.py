@@ -42,24 +42,11 @@ import closed_loop as CL
 import fb_dynamics as F
 import fb_models as FM
 from blf import native
+from gpu_util import dev_contacts, to_device as _d
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
 rel_err = FM.rel_err
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def dev_contacts(ct, B):
-    """The first B systems of the case's contacts on the device."""
-    if ct is None:
-        return None
-    dev = dict(frame=_d(ct["frame"], torch.int32), params=_d(ct["params"]), null_pose=_d(ct["null_pose"][:B]))
-    if ct["law"] is not None:
-        dev.update(law=_d(ct["law"], torch.int32), wrench=_d(ct["wrench"][:B]))
-    return dev
 
 
 def run_device(handle, cid, kind):

@@ -61,22 +61,12 @@ import ik_cases as IC
 import ik_reference as IK
 from blf import native
 from blf import problems as P
+from gpu_util import dev_contacts, to_device as _d
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
 rel_err = FM.rel_err
 RUN_IDS = [f"{c}-{s}" for c, s in FM.TRANSLATION_RUNS]
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def dev_contacts(ct, B):
-    dev = dict(frame=_d(ct["frame"], torch.int32), params=_d(ct["params"]), null_pose=_d(ct["null_pose"][:B]))
-    if ct["law"] is not None:
-        dev.update(law=_d(ct["law"], torch.int32), wrench=_d(ct["wrench"][:B]))
-    return dev
 
 
 @pytest.mark.parametrize("k", FM.SHIFTS)

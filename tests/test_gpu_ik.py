@@ -30,24 +30,12 @@ import fb_models as FM
 import ik_cases as IC
 import ik_reference as IK
 from blf import native
+from gpu_util import dev_state, dev_tasks, raises as _raises
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
 rel_err = FM.rel_err
 DT = 0.01
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def dev_state(states, rows=None):
-    rows = slice(None) if rows is None else rows
-    return {k: _d(states[k][rows]) for k in native.FB_STATE_KEYS}
-
-
-def dev_tasks(handle, model, tasks, B):
-    return handle.ik_tasks(B, model["n"], **tasks)
 
 
 def odd_outputs(B, NV):
@@ -245,12 +233,6 @@ def test_ik_optional_outputs_and_empty_batch(handle):
     empty = {k: v[:0] for k, v in dev_state(cs["states"]).items()}
     handle.fb_ik_solve(dm, empty, dev_tasks(handle, model, IK.tasks_rows(cs["tasks"], slice(0, 0)), 0))
     handle.fb_ik_integrate(dm, empty, dev_tasks(handle, model, IK.tasks_rows(cs["tasks"], slice(0, 0)), 0), 1, DT)
-
-
-def _raises(code, fn, *a, **kw):
-    with pytest.raises(native.BlfError) as e:
-        fn(*a, **kw)
-    assert e.value.code == code, (e.value.code, str(e.value))
 
 
 def test_ik_call_errors(handle):

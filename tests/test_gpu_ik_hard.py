@@ -32,6 +32,7 @@ import ik_hard_cases as HC
 import ik_hard_reference as HR
 import ik_reference as IK
 from blf import native, robot
+from gpu_util import dev_state, dev_tasks, raises as _raises
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -39,19 +40,7 @@ rel_err = FM.rel_err
 DT = HC.DT
 
 
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def dev_state(states, rows=None):
-    rows = slice(None) if rows is None else rows
-    return {k: _d(states[k][rows]) for k in native.FB_STATE_KEYS}
-
-
-def dev_tasks(handle, model, tasks, B):
-    return handle.ik_tasks(B, model["n"], **tasks)
-
-
+# local: the mask of a case, with a pivot threshold
 def hard_of(cs, tau=0.0):
     h = native.IkHard()
     h.rows, h.reserved, h.rel_pivot_min = cs["rows"], 0, tau
@@ -313,12 +302,6 @@ def test_rel_pivot_min_is_honoured(handle):
     nu, status = solve_hard(handle, cs, hard=hard_of(cs, 1e-3))
     assert (status == HR.OK).all()
     np.testing.assert_array_equal(nu, nu0)
-
-
-def _raises(code, fn, *a, **kw):
-    with pytest.raises(native.BlfError) as e:
-        fn(*a, **kw)
-    assert e.value.code == code, (e.value.code, str(e.value))
 
 
 def test_hard_call_errors(handle):

@@ -30,6 +30,7 @@ import ik_limits_cases as LC
 import ik_limits_reference as LR
 import ik_reference as IK
 from blf import native, robot
+from gpu_util import dev_state, raises as _raises
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -37,15 +38,7 @@ rel_err = FM.rel_err
 DT = LC.DT
 
 
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def dev_state(states, rows=None):
-    rows = slice(None) if rows is None else rows
-    return {k: _d(states[k][rows]) for k in native.FB_STATE_KEYS}
-
-
+# local: the mask of a case, None for a case without hard rows
 def hard_of(cs):
     if cs["rows"] == 0:
         return None
@@ -54,6 +47,7 @@ def hard_of(cs):
     return h
 
 
+# local: one (word 0, word 1) pair per robot of a solve's active set
 def masks_of(active):
     a = active.cpu().numpy().astype(np.uint64)
     return [(int(a[i, 0]), int(a[i, 1])) for i in range(a.shape[0])]
@@ -260,12 +254,6 @@ def test_status_precedence_and_containment(handle):
     for i in (0, 2):
         assert status[i] == LR.OK and iters[i] == good[2][i] and act[i] == good[3][i]
         np.testing.assert_array_equal(nu[i], good[0][i])
-
-
-def _raises(code, fn, *a, **kw):
-    with pytest.raises(native.BlfError) as e:
-        fn(*a, **kw)
-    assert e.value.code == code, (e.value.code, str(e.value))
 
 
 def test_limits_call_errors(handle):

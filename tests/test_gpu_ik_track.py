@@ -31,6 +31,7 @@ import ik_limits_reference as LR
 import ik_track_cases as TC
 import ik_track_reference as TR
 from blf import native
+from gpu_util import dev_state, to_device as _d
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -40,15 +41,7 @@ DT = TC.DT
 OUT = ("joint_traj", "base_traj", "nu_traj", "status", "fail_step", "iters", "active")
 
 
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def dev_state(states, rows=None):
-    rows = slice(None) if rows is None else rows
-    return {k: _d(states[k][rows]) for k in native.FB_STATE_KEYS}
-
-
+# local: the mask as a number, None for 0
 def hard_of(rows):
     if rows == 0:
         return None
@@ -97,6 +90,7 @@ def run_track(handle, cs, robots=None, steps=None, schedule=None, limits="case",
     return out, {k: v.cpu().numpy() for k, v in st.items()}
 
 
+# local: robot i's (word 0, word 1) of a host array
 def masks_of(active, i):
     a = active.astype(np.uint64)
     return (int(a[i, 0]), int(a[i, 1]))

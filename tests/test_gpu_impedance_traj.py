@@ -10,18 +10,11 @@ import torch
 
 import impedance_traj_cases as TC
 from blf import native
+from gpu_util import assert_bitwise, rel_err, to_device as _d
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
 T0, T1, DT = TC.T0, TC.T1, TC.DT
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
-def rel_err(a, b):
-    return np.abs(a - b).max() / max(1.0, np.abs(b).max())
 
 
 def dev_case(handle, cid, B):
@@ -49,12 +42,6 @@ def run_held(handle, cid, B, q_ref, mass_reg=None):
                                          mass_reg=None if mass_reg is None else _d(mass_reg))
     torch.cuda.synchronize()
     return {k: v.cpu().numpy() for k, v in d["state"].items()}
-
-
-def assert_bitwise(a, b, robots=None):
-    for k in native.FB_STATE_KEYS:
-        x, y = (a[k], b[k]) if robots is None else (a[k][robots], b[k][robots])
-        np.testing.assert_array_equal(x, y, err_msg=k)
 
 
 def assert_close(got, ref, what):

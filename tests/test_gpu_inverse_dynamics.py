@@ -15,6 +15,7 @@ import inverse_dynamics_reference as ID
 from blf import native
 from blf import robot
 from blf.closed_loop import fixed_step_schedule
+from gpu_util import assert_bitwise, dev_contacts, to_device as _d
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -23,23 +24,11 @@ KP, KD = 400.0, 40.0   # 20 rad/s, critically damped: sqrt(kp) h = 0.04 at the s
 SCHEDULE = fixed_step_schedule(TC.T0, TC.T1, TC.DT)
 
 
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
-
-
 def _np(d):
     return {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in d.items()}
 
 
-def dev_contacts(ct, B):
-    if ct is None:
-        return None
-    out = dict(frame=_d(ct["frame"], torch.int32), params=_d(ct["params"]), null_pose=_d(ct["null_pose"][:B]))
-    if ct.get("law") is not None:
-        out.update(law=_d(ct["law"], torch.int32), wrench=_d(ct["wrench"][:B]))
-    return out
-
-
+# local: the first B robots of the state (gpu_util.dev_state takes an index set)
 def dev_state(st, B):
     return {k: _d(st[k][:B]) for k in native.FB_STATE_KEYS}
 
@@ -290,12 +279,6 @@ def run_ct(handle, cid, B, q_ref, sps=5, nu=None, qdd=None, q_bias=None, tau_max
 
 def full(handle, cid, B, r, **kw):
     return run_ct(handle, cid, B, r["q_ref"], nu=r["nu"], qdd=r["qdd"], q_bias=r["q_bias"], **kw)
-
-
-def assert_bitwise(a, b, robots=None):
-    for k in native.FB_STATE_KEYS:
-        x, y = (a[k], b[k]) if robots is None else (a[k][robots], b[k][robots])
-        np.testing.assert_array_equal(x, y, err_msg=k)
 
 
 @pytest.mark.parametrize("cid,B", [("h24", 3), ("h24p", 3), ("n48", 2)])

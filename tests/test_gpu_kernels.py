@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
+# local: torch.from_numpy, then the conversion (gpu_util.to_device converts in torch.as_tensor)
 def _d(a, dtype=torch.float64):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).cuda()
 

@@ -18,8 +18,9 @@ STEPS = (1, 2, 7)
 BMAX, TMAX = max(BATCHES), max(STEPS)
 
 
+# local: fp64 only, and the host array is always copied first (gpu_util.to_device copies only if it must)
 def _d(a):
-    return torch.from_numpy(np.array(a, dtype=np.float64, order="C")).cuda()   # always a copy
+    return torch.from_numpy(np.array(a, dtype=np.float64, order="C")).cuda()
 
 
 def _d_unaligned(a):

@@ -11,6 +11,7 @@ from blf import native
 pytestmark = pytest.mark.gpu
 
 
+# local: gpu_util.to_device with a misaligned form
 def _d(a, dtype=torch.float64, misalign=False):
     """Device copy of `a`; with misalign=True its data pointer is 8 B past a 16-B boundary."""
     a = np.ascontiguousarray(a)

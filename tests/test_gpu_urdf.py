@@ -9,14 +9,11 @@ import torch
 
 import fb_dynamics as F
 from blf import native, robot, urdf
+from gpu_util import to_device as _d
 from test_urdf import MODEL, to_urdf
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
-
-
-def _d(a, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).cuda()
 
 
 def test_urdf_model_euler_with_contacts_vs_oracle(handle):

@@ -5,16 +5,13 @@ as the stand-alone ASan + UBSan binary; on a GPU finalize()'s refusals (sizes, "
 model without limits), advance() against blf_fb_ik_solve_limits with a bound active, and advance()
 false on limits that leave the hard feet no solution.  And, on the CPU, that the two URDF loaders
 (blf/urdf.py, blf::loadUrdf) read equal limits from one document."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "bipedal-locomotion-framework_amd")
-BIN = os.path.join(PKG, "lib", "blf_ik_limits_tests")
-BIN_ASAN = os.path.join(PKG, "lib", "blf_ik_limits_tests_asan")
+import host_binaries as HB
+
 CPU_CASES = ("JointLimitsTask keys", "QPInverseKinematics limits task bookkeeping", "loadUrdf joint limits")
 GPU_CASES = ("QPInverseKinematics limits finalize", "QPInverseKinematics limits on the device",
              "QPInverseKinematics infeasible limits")
@@ -36,41 +33,17 @@ URDF = """<?xml version="1.0"?>
 """
 
 
-def _build():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-s", "-j8", "-C", PKG])
-
-
-def _run(binary, which, extra_env=None):
-    env = dict(os.environ, **(extra_env or {}))
-    r = subprocess.run([binary, which], capture_output=True, text=True, timeout=600, env=env)
-    assert "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "runtime error:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, r.stdout + r.stderr[-4000:]
-    assert "0 failed" in r.stdout, r.stdout
-    return r.stdout
-
-
-def _ok(out, name):
-    return any(line.startswith(name) and line.rstrip().endswith("ok") for line in out.splitlines())
-
-
 def test_ik_limits_adapter_bookkeeping():
-    _build()
-    out = _run(BIN, "cpu")
-    for name in CPU_CASES:
-        assert _ok(out, name), out
+    out, _ = HB.run("ik_limits_tests", "cpu")
+    HB.assert_cases_ok(out, CPU_CASES)
 
 
 def test_ik_limits_adapter_asan_cpu():
     """The instrumented stand-alone binary (make asan), host-only cases: leak detection on, every
     UBSan finding aborts."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", PKG, "asan"])
-    out = _run(BIN_ASAN, "cpu",
-               dict(ASAN_OPTIONS="halt_on_error=1:exitcode=99:detect_leaks=1",
-                    UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    for name in CPU_CASES:
-        assert _ok(out, name), out
+    HB.build_asan()
+    out, _ = HB.run("ik_limits_tests", "cpu", asan=True)
+    HB.assert_cases_ok(out, CPU_CASES)
 
 
 def test_urdf_loaders_read_equal_limits(tmp_path):
@@ -79,12 +52,12 @@ def test_urdf_loaders_read_equal_limits(tmp_path):
     joint, after the fixed joint is merged; the continuous joint and the joint without <limit> have no
     range, the prismatic joint no velocity limit."""
     from blf import urdf
-    _build()
+    HB.ensure_built("ik_limits_tests")
     path = tmp_path / "limits.urdf"
     path.write_text(URDF)
     model = urdf.load_urdf(str(path))
     lim = urdf.load_urdf_limits(str(path), model)
-    r = subprocess.run([BIN, "urdf", str(path)], capture_output=True, text=True, timeout=60)
+    r = subprocess.run([HB.binary("ik_limits_tests"), "urdf", str(path)], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     rows = [line.split() for line in r.stdout.splitlines()]
     assert [row[0] for row in rows] == list(model["names"][1:]) == ["shoulder", "spin", "slide", "wrist"]
@@ -101,6 +74,5 @@ def test_urdf_loaders_read_equal_limits(tmp_path):
 
 @pytest.mark.gpu
 def test_ik_limits_adapter_on_device():
-    out = _run(BIN, "gpu")
-    for name in GPU_CASES:
-        assert _ok(out, name), out
+    out, _ = HB.run("ik_limits_tests", "gpu")
+    HB.assert_cases_ok(out, GPU_CASES)

@@ -3,32 +3,13 @@
 model, plain and as the stand-alone ASan + UBSan binary; on a GPU the round trip (the torques of
 inverseDynamics set as the control input, dynamics() returns the requested joint accelerations and the same
 base acceleration), free fall, and the refusals of a wrong size and of a robot the device reports failed."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "bipedal-locomotion-framework_amd")
-BIN = os.path.join(PKG, "lib", "blf_invdyn_tests")
-BIN_ASAN = os.path.join(PKG, "lib", "blf_invdyn_tests_asan")
+import host_binaries as HB
+
 CPU_CASES = ("FloatingBaseDynamicalSystem inverseDynamics refusals",)
 GPU_CASES = ("FloatingBaseDynamicalSystem inverseDynamics on the device",)
 TAG = "[FloatingBaseDynamicalSystem::inverseDynamics] "
-
-
-def _run(binary, which, extra_env=None):
-    env = dict(os.environ, **(extra_env or {}))
-    r = subprocess.run([binary, which], capture_output=True, text=True, timeout=600, env=env)
-    assert "ERROR: AddressSanitizer" not in r.stderr, r.stderr[-4000:]
-    assert "runtime error:" not in r.stderr, r.stderr[-4000:]
-    assert r.returncode == 0, r.stdout + r.stderr[-4000:]
-    assert "0 failed" in r.stdout, r.stdout
-    return r.stdout, r.stderr
-
-
-def _ok(out, name):
-    return any(line.startswith(name) and line.rstrip().endswith("ok") for line in out.splitlines())
 
 
 def _lines(err):
@@ -36,29 +17,22 @@ def _lines(err):
 
 
 def test_invdyn_adapter_refusals():
-    if not os.path.exists(BIN):
-        subprocess.check_call(["make", "-s", "-j8", "-C", PKG])
-    out, err = _run(BIN, "cpu")
-    for name in CPU_CASES:
-        assert _ok(out, name), out
+    out, err = HB.run("invdyn_tests", "cpu")
+    HB.assert_cases_ok(out, CPU_CASES)
     assert any("setRobotModel" in l for l in _lines(err)), err
 
 
 def test_invdyn_adapter_asan_cpu():
     """The instrumented stand-alone binary (make asan), host-only cases: leak detection on, every
     UBSan finding aborts."""
-    subprocess.check_call(["make", "-s", "-j8", "-C", PKG, "asan"])
-    out, _ = _run(BIN_ASAN, "cpu",
-                  dict(ASAN_OPTIONS="halt_on_error=1:exitcode=99:detect_leaks=1",
-                       UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    for name in CPU_CASES:
-        assert _ok(out, name), out
+    HB.build_asan()
+    out, _ = HB.run("invdyn_tests", "cpu", asan=True)
+    HB.assert_cases_ok(out, CPU_CASES)
 
 
 @pytest.mark.gpu
 def test_invdyn_adapter_on_device():
-    out, err = _run(BIN, "gpu")
-    for name in GPU_CASES:
-        assert _ok(out, name), out
+    out, err = HB.run("invdyn_tests", "gpu")
+    HB.assert_cases_ok(out, GPU_CASES)
     for word in ("Wrong size", "The device reports"):
         assert any(word in l for l in _lines(err)), (word, err)
