@@ -18,23 +18,6 @@ STATUS_NAMES = {0: "BLF_OK", 1: "BLF_ERR_INVALID_ARGUMENT", 2: "BLF_ERR_HIP",
                 3: "BLF_ERR_UNSUPPORTED", 4: "BLF_ERR_TIME_INTERVAL", 5: "BLF_ERR_EMPTY_INTERVAL"}
 QP_SOLVED, QP_MAX_ITER, QP_NUMERICAL, QP_BAD_FACETS = 0, 1, 2, 3
 
-# every symbol include/blf/blf_c.h declares (tests/test_abi.py checks the .so exports them)
-EXPORTED = ["blf_create", "blf_destroy", "blf_last_error", "blf_version", "blf_set_qp_launch_mode",
-            "blf_step_schedule",
-            "blf_lti_euler_integrate", "blf_lti_dynamics", "blf_dcm_euler_rollout", "blf_hull2d_hrep",
-            "blf_hull2d_contains", "blf_hull3d_hrep", "blf_hullnd_hrep", "blf_halfspace_contains", "blf_quintic_fit", "blf_quintic_eval",
-            "blf_dcm_mpc_default_params", "blf_dcm_mpc_solve", "blf_dcm_mpc_solve_warm",
-            "blf_dcm_phase_expand", "blf_dcm_mpc_solve_phased",
-            "blf_dcm_mpc_flops_per_iter",
-            "blf_contact_model_eval", "blf_contact_point_wrench", "blf_fbk_dynamics",
-            "blf_fbk_euler_integrate", "blf_fbd_dynamics", "blf_fbd_euler_integrate",
-            "blf_fb_dcm", "blf_dcm_posture_reference", "blf_fbd_euler_integrate_impedance",
-            "blf_fb_frame_state", "blf_rls_advance", "blf_contact_rls_advance",
-            "blf_swing_foot_eval", "blf_so3_eval", "blf_fb_ik_solve", "blf_fb_ik_integrate",
-            "blf_fb_ik_solve_hard", "blf_fb_ik_integrate_hard", "blf_fb_ik_solve_limits",
-            "blf_fb_ik_integrate_limits", "blf_fb_ik_track",
-            "blf_fbd_euler_integrate_impedance_traj", "blf_dcm_com_reference",
-            "blf_fb_inverse_dynamics", "blf_fbd_euler_integrate_computed_torque_traj"]
 # entry points removed in round 5 (measured slower, never the default; tests/test_abi.py checks
 # that the library no longer exports them)
 REMOVED = ["blf_set_qp_split_batch", "blf_stream_create_cu_range", "blf_stream_destroy",
@@ -171,15 +154,108 @@ class DcmMpcWarmStart(ctypes.Structure):
                 ("floor", _f64), ("prev_status", _vp)]
 
 
-def _warm_start(warm, B, N, M):
-    """blf_dcm_mpc_warm_start from a dict: vrp [B,N,2], lam [B,N,M], shift, floor and optionally
-    status [B] int32 (the previous solve's statuses: problems with status != 0 start cold)."""
-    torch = _torch()
-    st = warm.get("status")
-    return DcmMpcWarmStart(_ptr(warm["vrp"], torch.float64, (B, N, 2), "warm vrp"),
-                           _ptr(warm["lam"], torch.float64, (B, N, M), "warm lam"),
-                           int(warm.get("shift", 1)), 0, float(warm.get("floor", 1e-2)),
-                           _ptr(st, torch.int32, (B,), "warm status") if st is not None else None)
+def _sig(restype=_i32, **args):
+    """A SIGNATURES entry: (result ctype, ((argument name, ctype), ...)); blf_status unless given."""
+    return restype, tuple(args.items())
+
+
+_P = ctypes.POINTER
+_FB = dict(handle=_vp, model=_P(FbModel), state=_P(FbState))
+_TIMES = dict(initial_time=_f64, final_time=_f64, dT=_f64)
+# Every entry point include/blf/blf_c.h declares: its result type and its (argument name, ctype) pairs in the
+# header's order (lambda_: the header's `lambda`).  lib() sets the prototypes from it; tests/test_abi.py parses
+# the header and checks the table and the struct classes against it, and that the .so exports every name.
+SIGNATURES = {
+    "blf_create": _sig(handle=_P(_vp), device=_i32),
+    "blf_destroy": _sig(handle=_vp),
+    "blf_last_error": _sig(ctypes.c_char_p),
+    "blf_version": _sig(ctypes.c_char_p),
+    "blf_set_qp_launch_mode": _sig(fuse_stage2=_i32, single_kernel=_i32),
+    "blf_step_schedule": _sig(**_TIMES, iterations=_vp, dT_last=_vp, t_last=_vp),
+    "blf_lti_euler_integrate": _sig(handle=_vp, n=_i32, m=_i32, A=_vp, Bm=_vp, shared_matrices=_i32, u=_vp,
+        x=_vp, batch=_i64, **_TIMES, stream=_vp),
+    "blf_lti_dynamics": _sig(handle=_vp, n=_i32, m=_i32, A=_vp, Bm=_vp, shared_matrices=_i32, u=_vp, x=_vp,
+        dx=_vp, batch=_i64, stream=_vp),
+    "blf_dcm_euler_rollout": _sig(handle=_vp, xi0=_vp, omega=_vp, vrp=_vp, horizon=_i32, dt=_f64, xi_out=_vp,
+        batch=_i64, stream=_vp),
+    "blf_hull2d_hrep": _sig(handle=_vp, pts=_vp, npts=_vp, max_points=_i32, max_facets=_i32, batch=_i64, A=_vp,
+        b=_vp, nfacets=_vp, stream=_vp),
+    "blf_hull2d_contains": _sig(handle=_vp, A=_vp, b=_vp, nfacets=_vp, max_facets=_i32, query=_vp, batch=_i64,
+        inside=_vp, stream=_vp),
+    "blf_hull3d_hrep": _sig(handle=_vp, pts=_vp, npts=_vp, max_points=_i32, max_facets=_i32, batch=_i64, A=_vp,
+        b=_vp, nfacets=_vp, stream=_vp),
+    "blf_hullnd_hrep": _sig(handle=_vp, dim=_i32, pts=_vp, npts=_vp, max_points=_i32, max_facets=_i32,
+        batch=_i64, A=_vp, b=_vp, nfacets=_vp, stream=_vp),
+    "blf_halfspace_contains": _sig(handle=_vp, A=_vp, b=_vp, nfacets=_vp, dim=_i32, max_facets=_i32, query=_vp,
+        batch=_i64, inside=_vp, stream=_vp),
+    "blf_quintic_fit": _sig(handle=_vp, knots_t=_vp, knots_pva=_vp, nknots=_i32, dim=_i32, nsplines=_i64,
+        coeffs=_vp, stream=_vp),
+    "blf_quintic_eval": _sig(handle=_vp, knots_t=_vp, coeffs=_vp, nknots=_i32, dim=_i32, nsplines=_i64, tq=_vp,
+        nq=_i32, pva=_vp, knot_idx=_vp, stream=_vp),
+    "blf_dcm_mpc_default_params": _sig(None, p=_P(DcmMpcParams), horizon=_i32),
+    "blf_dcm_mpc_solve": _sig(handle=_vp, params=_P(DcmMpcParams), problem=_P(DcmMpcProblem), batch=_i64,
+        solution=_P(DcmMpcSolution), stream=_vp),
+    "blf_dcm_mpc_solve_warm": _sig(handle=_vp, params=_P(DcmMpcParams), problem=_P(DcmMpcProblem),
+        warm=_P(DcmMpcWarmStart), batch=_i64, solution=_P(DcmMpcSolution), lambda_out=_vp, stream=_vp),
+    "blf_dcm_phase_expand": _sig(handle=_vp, phases=_P(PhaseTable), start_knot=_i64, dt=_f64, horizon=_i32,
+        batch=_i64, A=_vp, b=_vp, nfacets=_vp, xi_ref=_vp, vrp_ref=_vp, stream=_vp),
+    "blf_dcm_mpc_solve_phased": _sig(handle=_vp, params=_P(DcmMpcParams), phases=_P(PhaseTable),
+        start_knot=_i64, xi_init=_vp, omega=_vp, omega_stride=_i64, warm=_P(DcmMpcWarmStart), batch=_i64,
+        window=_P(DcmMpcWindow), solution=_P(DcmMpcSolution), lambda_out=_vp, stream=_vp),
+    "blf_dcm_mpc_flops_per_iter": _sig(_f64, horizon=_i32, active_facets=_i64),
+    "blf_contact_model_eval": _sig(handle=_vp, params=_vp, shared_params=_i32, twist=_vp, pose=_vp,
+        null_pose=_vp, batch=_i64, wrench=_vp, autonomous=_vp, control=_vp, regressor=_vp, stream=_vp),
+    "blf_contact_point_wrench": _sig(handle=_vp, params=_vp, shared_params=_i32, twist=_vp, pose=_vp,
+        null_pose=_vp, batch=_i64, points=_vp, npoints=_i32, force=_vp, torque=_vp, stream=_vp),
+    "blf_fbk_dynamics": _sig(handle=_vp, ndof=_i32, rho=_f64, rot=_vp, twist=_vp, joint_vel=_vp, dpos=_vp,
+        drot=_vp, djoints=_vp, batch=_i64, stream=_vp),
+    "blf_fbk_euler_integrate": _sig(handle=_vp, ndof=_i32, rho=_f64, pos=_vp, rot=_vp, joints=_vp, twist=_vp,
+        joint_vel=_vp, batch=_i64, **_TIMES, stream=_vp),
+    "blf_fbd_dynamics": _sig(**_FB, joint_torque=_vp, contacts=_P(FbContacts), mass_reg=_vp, batch=_i64,
+        out=_P(FbState), stream=_vp),
+    "blf_fbd_euler_integrate": _sig(**_FB, joint_torque=_vp, contacts=_P(FbContacts), mass_reg=_vp, batch=_i64,
+        **_TIMES, stream=_vp),
+    "blf_fb_dcm": _sig(**_FB, omega0=_vp, omega0_stride=_i64, batch=_i64, com=_vp, xi=_vp, stream=_vp),
+    "blf_dcm_posture_reference": _sig(handle=_vp, law=_P(PostureLaw), com=_vp, vrp=_vp, vrp_stride=_i64,
+        batch=_i64, q_ref=_vp, stream=_vp),
+    "blf_fbd_euler_integrate_impedance": _sig(**_FB, impedance=_P(JointImpedance), contacts=_P(FbContacts),
+        mass_reg=_vp, batch=_i64, **_TIMES, stream=_vp),
+    "blf_fb_frame_state": _sig(**_FB, nframes=_i32, frames=_vp, batch=_i64, pose=_vp, twist=_vp, stream=_vp),
+    "blf_rls_advance": _sig(handle=_vp, n=_i32, m=_i32, lambda_=_f64, meas_cov=_vp, shared_cov=_i32,
+        regressor=_vp, measurements=_vp, steps=_i32, state=_vp, covariance=_vp, batch=_i64, stream=_vp),
+    "blf_contact_rls_advance": _sig(handle=_vp, lambda_=_f64, meas_cov=_vp, shared_cov=_i32, geometry=_vp,
+        shared_geometry=_i32, twist=_vp, pose=_vp, null_pose=_vp, wrench=_vp, steps=_i32, state=_vp,
+        covariance=_vp, batch=_i64, stream=_vp),
+    "blf_swing_foot_eval": _sig(handle=_vp, params=_P(SwingFootParams), contact_pose=_vp, contact_time=_vp,
+        ncontacts=_vp, batch=_i64, tq=_vp, nq=_i32, pose=_vp, twist=_vp, accel=_vp, contact_idx=_vp,
+        in_contact=_vp, stream=_vp),
+    "blf_so3_eval": _sig(handle=_vp, R0=_vp, R1=_vp, duration=_vp, batch=_i64, tq=_vp, nq=_i32, rot=_vp,
+        omega=_vp, alpha=_vp, stream=_vp),
+    "blf_fb_ik_solve": _sig(**_FB, tasks=_P(IkTasks), batch=_i64, nu=_vp, status=_vp, stream=_vp),
+    "blf_fb_ik_integrate": _sig(**_FB, tasks=_P(IkTasks), batch=_i64, steps=_i32, dT=_f64, nu=_vp, status=_vp,
+        stream=_vp),
+    "blf_fb_ik_solve_hard": _sig(**_FB, tasks=_P(IkTasks), hard=_P(IkHard), batch=_i64, nu=_vp, status=_vp,
+        stream=_vp),
+    "blf_fb_ik_integrate_hard": _sig(**_FB, tasks=_P(IkTasks), hard=_P(IkHard), batch=_i64, steps=_i32, dT=_f64,
+        nu=_vp, status=_vp, stream=_vp),
+    "blf_fb_ik_solve_limits": _sig(**_FB, tasks=_P(IkTasks), hard=_P(IkHard), limits=_P(IkLimits), batch=_i64,
+        nu=_vp, status=_vp, iters=_vp, active=_vp, stream=_vp),
+    "blf_fb_ik_integrate_limits": _sig(**_FB, tasks=_P(IkTasks), hard=_P(IkHard), limits=_P(IkLimits),
+        batch=_i64, steps=_i32, dT=_f64, nu=_vp, status=_vp, iters=_vp, active=_vp, stream=_vp),
+    "blf_fb_ik_track": _sig(**_FB, tasks=_P(IkTasks), hard=_P(IkHard), limits=_P(IkLimits),
+        schedule=_P(IkSchedule), batch=_i64, dT=_f64, joint_traj=_vp, base_traj=_vp, nu_traj=_vp, status=_vp,
+        fail_step=_vp, iters=_vp, active=_vp, stream=_vp),
+    "blf_fbd_euler_integrate_impedance_traj": _sig(**_FB, impedance=_P(JointImpedanceTraj),
+        contacts=_P(FbContacts), mass_reg=_vp, batch=_i64, **_TIMES, stream=_vp),
+    "blf_dcm_com_reference": _sig(handle=_vp, xi0=_vp, vrp=_vp, vrp_stride=_i64, omega0=_vp, omega0_stride=_i64,
+        z_ref=_vp, c_ref=_vp, steps=_i32, dT=_f64, batch=_i64, com_pos=_vp, com_vel=_vp, xi_end=_vp,
+        stream=_vp),
+    "blf_fb_inverse_dynamics": _sig(**_FB, joint_acc=_vp, base_acc=_vp, contacts=_P(FbContacts), batch=_i64,
+        joint_torque=_vp, base_acc_out=_vp, base_wrench=_vp, status=_vp, reserved=_i32, stream=_vp),
+    "blf_fbd_euler_integrate_computed_torque_traj": _sig(**_FB, law=_P(ComputedTorqueTraj),
+        contacts=_P(FbContacts), mass_reg=_vp, batch=_i64, **_TIMES, stream=_vp),
+}
+EXPORTED = list(SIGNATURES)
 
 
 _LIB = None
@@ -201,105 +277,9 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        L.blf_create.argtypes = [ctypes.POINTER(_vp), _i32]
-        L.blf_destroy.argtypes = [_vp]
-        L.blf_last_error.restype = ctypes.c_char_p
-        L.blf_version.restype = ctypes.c_char_p
-        L.blf_lti_euler_integrate.argtypes = [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _i64,
-                                              _f64, _f64, _f64, _vp]
-        L.blf_lti_dynamics.argtypes = [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp]
-        L.blf_dcm_euler_rollout.argtypes = [_vp, _vp, _vp, _vp, _i32, _f64, _vp, _i64, _vp]
-        L.blf_hull2d_hrep.argtypes = [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]
-        L.blf_hull2d_contains.argtypes = [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp]
-        L.blf_hull3d_hrep.argtypes = [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]
-        L.blf_hullnd_hrep.argtypes = [_vp, _i32, _vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]
-        L.blf_halfspace_contains.argtypes = [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp]
-        L.blf_quintic_fit.argtypes = [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp]
-        L.blf_quintic_eval.argtypes = [_vp, _vp, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _vp]
-        L.blf_dcm_mpc_default_params.argtypes = [ctypes.POINTER(DcmMpcParams), _i32]
-        L.blf_dcm_mpc_default_params.restype = None
-        L.blf_dcm_mpc_solve.argtypes = [_vp, ctypes.POINTER(DcmMpcParams),
-                                        ctypes.POINTER(DcmMpcProblem), _i64,
-                                        ctypes.POINTER(DcmMpcSolution), _vp]
-        L.blf_dcm_mpc_solve_warm.argtypes = [_vp, ctypes.POINTER(DcmMpcParams),
-                                             ctypes.POINTER(DcmMpcProblem),
-                                             ctypes.POINTER(DcmMpcWarmStart), _i64,
-                                             ctypes.POINTER(DcmMpcSolution), _vp, _vp]
-        L.blf_dcm_phase_expand.argtypes = [_vp, ctypes.POINTER(PhaseTable), _i64, _f64, _i32,
-                                           _i64, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.blf_dcm_mpc_solve_phased.argtypes = [_vp, ctypes.POINTER(DcmMpcParams),
-                                               ctypes.POINTER(PhaseTable), _i64, _vp, _vp, _i64,
-                                               ctypes.POINTER(DcmMpcWarmStart), _i64,
-                                               ctypes.POINTER(DcmMpcWindow),
-                                               ctypes.POINTER(DcmMpcSolution), _vp, _vp]
-        L.blf_dcm_mpc_flops_per_iter.argtypes = [_i32, _i64]
-        L.blf_contact_model_eval.argtypes = [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
-                                             _vp, _vp]
-        L.blf_contact_point_wrench.argtypes = [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i32,
-                                               _vp, _vp, _vp]
-        L.blf_fbk_dynamics.argtypes = [_vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
-        L.blf_fbk_euler_integrate.argtypes = [_vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _i64,
-                                              _f64, _f64, _f64, _vp]
-        L.blf_fbd_dynamics.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), _vp,
-                                       ctypes.POINTER(FbContacts), _vp, _i64,
-                                       ctypes.POINTER(FbState), _vp]
-        L.blf_fbd_euler_integrate.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                              _vp, ctypes.POINTER(FbContacts), _vp, _i64, _f64,
-                                              _f64, _f64, _vp]
-        L.blf_fb_dcm.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), _vp, _i64,
-                                 _i64, _vp, _vp, _vp]
-        L.blf_dcm_posture_reference.argtypes = [_vp, ctypes.POINTER(PostureLaw), _vp, _vp, _i64, _i64,
-                                                _vp, _vp]
-        L.blf_fbd_euler_integrate_impedance.argtypes = [
-            _vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), ctypes.POINTER(JointImpedance),
-            ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
-        L.blf_fbd_euler_integrate_impedance_traj.argtypes = [
-            _vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), ctypes.POINTER(JointImpedanceTraj),
-            ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
-        L.blf_fb_inverse_dynamics.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), _vp, _vp,
-                                              ctypes.POINTER(FbContacts), _i64, _vp, _vp, _vp, _vp, _i32, _vp]
-        L.blf_fbd_euler_integrate_computed_torque_traj.argtypes = [
-            _vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), ctypes.POINTER(ComputedTorqueTraj),
-            ctypes.POINTER(FbContacts), _vp, _i64, _f64, _f64, _f64, _vp]
-        L.blf_dcm_com_reference.argtypes = [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _f64, _i64,
-                                            _vp, _vp, _vp, _vp]
-        L.blf_fb_frame_state.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState), _i32,
-                                         _vp, _i64, _vp, _vp, _vp]
-        L.blf_rls_advance.argtypes = [_vp, _i32, _i32, _f64, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
-                                      _i64, _vp]
-        L.blf_contact_rls_advance.argtypes = [_vp, _f64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp,
-                                              _i32, _vp, _vp, _i64, _vp]
-        L.blf_swing_foot_eval.argtypes = [_vp, ctypes.POINTER(SwingFootParams), _vp, _vp, _vp, _i64,
-                                          _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]
-        L.blf_so3_eval.argtypes = [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp]
-        L.blf_fb_ik_solve.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                      ctypes.POINTER(IkTasks), _i64, _vp, _vp, _vp]
-        L.blf_fb_ik_integrate.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                          ctypes.POINTER(IkTasks), _i64, _i32, _f64, _vp, _vp, _vp]
-        L.blf_fb_ik_solve_hard.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                           ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard), _i64, _vp, _vp, _vp]
-        L.blf_fb_ik_integrate_hard.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                               ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard), _i64, _i32, _f64,
-                                               _vp, _vp, _vp]
-        L.blf_fb_ik_solve_limits.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                             ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard),
-                                             ctypes.POINTER(IkLimits), _i64, _vp, _vp, _vp, _vp, _vp]
-        L.blf_fb_ik_integrate_limits.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                                 ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard),
-                                                 ctypes.POINTER(IkLimits), _i64, _i32, _f64, _vp, _vp, _vp, _vp,
-                                                 _vp]
-        L.blf_fb_ik_track.argtypes = [_vp, ctypes.POINTER(FbModel), ctypes.POINTER(FbState),
-                                      ctypes.POINTER(IkTasks), ctypes.POINTER(IkHard), ctypes.POINTER(IkLimits),
-                                      ctypes.POINTER(IkSchedule), _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _vp]
-        L.blf_dcm_mpc_flops_per_iter.restype = _f64
-        L.blf_set_qp_launch_mode.argtypes = [_i32, _i32]
-        for name in EXPORTED:
-            if name not in ("blf_create", "blf_destroy", "blf_last_error", "blf_version",
-                            "blf_dcm_mpc_default_params", "blf_dcm_mpc_flops_per_iter"):
-                getattr(L, name).restype = _i32
-        L.blf_create.restype = _i32
-        L.blf_destroy.restype = _i32
+        for name, (restype, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, [t for _, t in args]
         _LIB = L
     return _LIB
 
@@ -400,6 +380,120 @@ def _stream(stream=None):
     return _vp(s.cuda_stream)
 
 
+def _ref(x):
+    """byref(x), or None (a null pointer) for None."""
+    return ctypes.byref(x) if x is not None else None
+
+
+def _upload(a, dtype, dev):
+    """A host array as a contiguous tensor on the device."""
+    return _torch().as_tensor(a, dtype=dtype).contiguous().to(dev)
+
+
+def _on_device(a, dtype, dev):
+    """A tensor as it stands (no copy; _ptr checks it later), a host array uploaded."""
+    return a if isinstance(a, _torch().Tensor) else _upload(a, dtype, dev)
+
+
+class _Held:
+    """A C struct (.c) with the tensors it points into (.t), kept alive together, and the sizes its builder
+    records for the calls that take it (.n, .batch, .nse3, .steps, .tau_last)."""
+
+    def __init__(self, c, t, **sizes):
+        self.c, self.t = c, t
+        self.__dict__.update(sizes)
+
+
+# A spec below is {name: (shape, torch dtype)} in the order of the C struct's members or the call's arguments.
+def _new(spec, dev):
+    torch = _torch()
+    return {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in spec.items()}
+
+
+def _ptrs(tensors, spec, prefix=""):
+    return [_ptr(tensors[k], dt, shape, prefix + k) for k, (shape, dt) in spec.items()]
+
+
+def _out(given, shape, dtype, dev, name, zero=False, optional=True):
+    """An output argument as (tensor, pointer).  None: allocated here (torch.zeros if `zero`, else
+    torch.empty); a tensor: checked and used; False, for an `optional` output: not requested, (None, None)."""
+    torch = _torch()
+    if given is False and optional:
+        return None, None
+    if given is None:
+        given = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=dev)
+    return given, _ptr(given, dtype, shape, name)
+
+
+def _outs(spec, given, dev, zero=False):
+    """_out over a spec: ({name: tensor or None}, [pointer or None])."""
+    pairs = {k: _out(given.get(k), shape, dt, dev, k, zero) for k, (shape, dt) in spec.items()}
+    return {k: t for k, (t, _) in pairs.items()}, [p for _, p in pairs.values()]
+
+
+def _requested(spec, outputs, out, dev):
+    """The `outputs=` form: the names in `outputs` are computed (into out[name] when `out` holds it), the
+    others are not requested.  Returns ({requested name: tensor}, [pointer or None for every name])."""
+    res, ptrs = _outs(spec, {k: (out or {}).get(k) if k in outputs else False for k in spec}, dev)
+    return {k: t for k, t in res.items() if k in outputs}, ptrs
+
+
+def _window_spec(B, N, M):
+    """A window's arrays in blf_dcm_mpc_window's order, which is blf_dcm_mpc_problem's after xi_init."""
+    f64, i32 = _torch().float64, _torch().int32
+    return dict(omega=((B, N), f64), xi_ref=((B, N + 1, 2), f64), vrp_ref=((B, N, 2), f64),
+                A=((B, N, M, 2), f64), b=((B, N, M), f64), nfacets=((B, N), i32))
+
+
+def _solution_spec(B, N):
+    f64, i32 = _torch().float64, _torch().int32
+    return dict(xi=((B, N + 1, 2), f64), vrp=((B, N, 2), f64), status=((B,), i32), iters=((B,), i32),
+                polished=((B,), i32), passes=((B,), i32))
+
+
+def _problem_struct(prob, B, N, M):
+    return DcmMpcProblem(_ptr(prob["xi_init"], _torch().float64, (B, 2), "xi_init"),
+                         *_ptrs(prob, _window_spec(B, N, M)))
+
+
+def _solution_struct(out, B, N):
+    """blf_dcm_mpc_solution over out; polished and passes are optional (absent: NULL, not written)."""
+    spec = {k: v for k, v in _solution_spec(B, N).items() if k in out or k not in ("polished", "passes")}
+    return DcmMpcSolution(**dict(zip(spec, _ptrs(out, spec))))
+
+
+def _lambda_out(out, wanted, B, N, M):
+    """The lambda_out pointer: out["lam"] [B,N,M] (allocated when absent), or None when not wanted."""
+    torch = _torch()
+    if not wanted:
+        return None
+    if "lam" not in out:
+        out["lam"] = torch.empty((B, N, M), dtype=torch.float64, device=out["xi"].device)
+    return _ptr(out["lam"], torch.float64, (B, N, M), "lam")
+
+
+def _warm_start(warm, B, N, M):
+    """blf_dcm_mpc_warm_start from a dict: vrp [B,N,2], lam [B,N,M], shift, floor and optionally
+    status [B] int32 (the previous solve's statuses: problems with status != 0 start cold)."""
+    torch = _torch()
+    st = warm.get("status")
+    return DcmMpcWarmStart(_ptr(warm["vrp"], torch.float64, (B, N, 2), "warm vrp"),
+                           _ptr(warm["lam"], torch.float64, (B, N, M), "warm lam"),
+                           int(warm.get("shift", 1)), 0, float(warm.get("floor", 1e-2)),
+                           _ptr(st, torch.int32, (B,), "warm status") if st is not None else None)
+
+
+def _phase_table_struct(table):
+    """(blf_phase_table, B, M) of a phase table dict (Handle.phase_table() or the same keys)."""
+    f64, i32 = _torch().float64, _torch().int32
+    B, P = table["phase_begin"].shape
+    M = table["phase_b"].shape[2]
+    spec = dict(nphases=((B,), i32), phase_begin=((B, P), f64), phase_end=((B, P), f64),
+                phase_A=((B, P, M, 2), f64), phase_b=((B, P, M), f64), phase_nf=((B, P), i32),
+                phase_ref=((B, P, 2), f64))
+    return PhaseTable(P, M, *_ptrs(table, spec)), B, M
+
+
 class Handle:
     """RAII wrapper of blf_handle (one per device per thread)."""
 
@@ -462,73 +556,46 @@ class Handle:
             _ptr(out, torch.float64, (B, N + 1, 2), "xi_out"), B, _stream(stream)))
         return out
 
-    def hull2d_hrep(self, pts, npts, max_facets=8, out=None, stream=None):
+    def _hull_hrep(self, fn, dim, D, pts, npts, max_facets, out, stream):
+        """blf_hull2d_hrep / blf_hull3d_hrep (dim = ()) and blf_hullnd_hrep (dim = (D,)) on pts [B, P, D]."""
         torch = _torch()
         B, P = pts.shape[0], pts.shape[1]
-        if out is None:
-            out = (torch.empty((B, max_facets, 2), dtype=torch.float64, device=pts.device),
-                   torch.empty((B, max_facets), dtype=torch.float64, device=pts.device),
-                   torch.empty((B,), dtype=torch.int32, device=pts.device))
-        A, b, nf = out
-        _check(lib().blf_hull2d_hrep(
-            self._h, _ptr(pts, torch.float64, (B, P, 2), "pts"), _ptr(npts, torch.int32, (B,), "npts"),
-            P, max_facets, B, _ptr(A, torch.float64, (B, max_facets, 2), "A"),
-            _ptr(b, torch.float64, (B, max_facets), "b"), _ptr(nf, torch.int32, (B,), "nfacets"),
-            _stream(stream)))
+        spec = dict(A=((B, max_facets, D), torch.float64), b=((B, max_facets), torch.float64),
+                    nfacets=((B,), torch.int32))
+        A, b, nf = out if out is not None else _new(spec, pts.device).values()
+        _check(fn(self._h, *dim, _ptr(pts, torch.float64, (B, P, D), "pts"), _ptr(npts, torch.int32, (B,), "npts"),
+                  P, max_facets, B, *_ptrs(dict(A=A, b=b, nfacets=nf), spec), _stream(stream)))
         return A, b, nf
 
-    def hullnd_hrep(self, pts, npts, max_facets=64, out=None, stream=None):
-        """blf_hullnd_hrep: pts [B, P, dim], npts [B] -> A [B, max_facets, dim], b, nfacets."""
-        torch = _torch()
-        B, P, D = pts.shape
-        if out is None:
-            out = (torch.empty((B, max_facets, D), dtype=torch.float64, device=pts.device),
-                   torch.empty((B, max_facets), dtype=torch.float64, device=pts.device),
-                   torch.empty((B,), dtype=torch.int32, device=pts.device))
-        A, b, nf = out
-        _check(lib().blf_hullnd_hrep(
-            self._h, D, _ptr(pts, torch.float64, (B, P, D), "pts"), _ptr(npts, torch.int32, (B,), "npts"),
-            P, max_facets, B, _ptr(A, torch.float64, (B, max_facets, D), "A"),
-            _ptr(b, torch.float64, (B, max_facets), "b"), _ptr(nf, torch.int32, (B,), "nfacets"),
-            _stream(stream)))
-        return A, b, nf
-
-    def hull2d_contains(self, A, b, nf, query, stream=None):
-        torch = _torch()
-        B, M = b.shape
-        inside = torch.empty((B,), dtype=torch.int32, device=A.device)
-        _check(lib().blf_hull2d_contains(
-            self._h, _ptr(A, torch.float64, (B, M, 2), "A"), _ptr(b, torch.float64, (B, M), "b"),
-            _ptr(nf, torch.int32, (B,), "nfacets"), M, _ptr(query, torch.float64, (B, 2), "query"),
-            B, _ptr(inside, torch.int32, (B,), "inside"), _stream(stream)))
-        return inside
+    def hull2d_hrep(self, pts, npts, max_facets=8, out=None, stream=None):
+        return self._hull_hrep(lib().blf_hull2d_hrep, (), 2, pts, npts, max_facets, out, stream)
 
     def hull3d_hrep(self, pts, npts, max_facets=32, out=None, stream=None):
         """blf_hull3d_hrep: pts [B, P, 3], npts [B] -> A [B, max_facets, 3], b, nfacets."""
+        return self._hull_hrep(lib().blf_hull3d_hrep, (), 3, pts, npts, max_facets, out, stream)
+
+    def hullnd_hrep(self, pts, npts, max_facets=64, out=None, stream=None):
+        """blf_hullnd_hrep: pts [B, P, dim], npts [B] -> A [B, max_facets, dim], b, nfacets."""
+        _, _, D = pts.shape
+        return self._hull_hrep(lib().blf_hullnd_hrep, (D,), D, pts, npts, max_facets, out, stream)
+
+    def _contains(self, fn, dim, B, M, D, A, b, nf, query, stream):
+        """blf_hull2d_contains (dim = ()) and blf_halfspace_contains (dim = (D,))."""
         torch = _torch()
-        B, P = pts.shape[0], pts.shape[1]
-        if out is None:
-            out = (torch.empty((B, max_facets, 3), dtype=torch.float64, device=pts.device),
-                   torch.empty((B, max_facets), dtype=torch.float64, device=pts.device),
-                   torch.empty((B,), dtype=torch.int32, device=pts.device))
-        A, b, nf = out
-        _check(lib().blf_hull3d_hrep(
-            self._h, _ptr(pts, torch.float64, (B, P, 3), "pts"), _ptr(npts, torch.int32, (B,), "npts"),
-            P, max_facets, B, _ptr(A, torch.float64, (B, max_facets, 3), "A"),
-            _ptr(b, torch.float64, (B, max_facets), "b"), _ptr(nf, torch.int32, (B,), "nfacets"),
-            _stream(stream)))
-        return A, b, nf
+        inside = torch.empty((B,), dtype=torch.int32, device=A.device)
+        _check(fn(self._h, _ptr(A, torch.float64, (B, M, D), "A"), _ptr(b, torch.float64, (B, M), "b"),
+                  _ptr(nf, torch.int32, (B,), "nfacets"), *dim, M, _ptr(query, torch.float64, (B, D), "query"),
+                  B, _ptr(inside, torch.int32, (B,), "inside"), _stream(stream)))
+        return inside
+
+    def hull2d_contains(self, A, b, nf, query, stream=None):
+        B, M = b.shape
+        return self._contains(lib().blf_hull2d_contains, (), B, M, 2, A, b, nf, query, stream)
 
     def halfspace_contains(self, A, b, nf, query, stream=None):
         """blf_halfspace_contains: A [B, M, dim], b [B, M], nf [B], query [B, dim] -> inside [B]."""
-        torch = _torch()
         B, M, D = A.shape
-        inside = torch.empty((B,), dtype=torch.int32, device=A.device)
-        _check(lib().blf_halfspace_contains(
-            self._h, _ptr(A, torch.float64, (B, M, D), "A"), _ptr(b, torch.float64, (B, M), "b"),
-            _ptr(nf, torch.int32, (B,), "nfacets"), D, M, _ptr(query, torch.float64, (B, D), "query"),
-            B, _ptr(inside, torch.int32, (B,), "inside"), _stream(stream)))
-        return inside
+        return self._contains(lib().blf_halfspace_contains, (D,), B, M, D, A, b, nf, query, stream)
 
     def quintic_fit(self, knots_t, knots_pva, stream=None):
         torch = _torch()
@@ -563,52 +630,22 @@ class Handle:
         (blf_dcm_mpc_solve_warm); lambda_out: also return the final multipliers out["lam"].
         out["polished"] [B] says which solutions are the certified active-set polish; out["passes"]
         [B] how many drop/add passes the active-set kernels ran for each."""
-        torch = _torch()
         B, N = prob["omega"].shape
         M = prob["b"].shape[2]
         p = params if params is not None else default_params(N, max_facets=M)
         if p.horizon != N or p.max_facets != M:
             raise ValueError("params.horizon / max_facets do not match the problem arrays")
-        dev = prob["omega"].device
         if out is None:
-            out = dict(xi=torch.empty((B, N + 1, 2), dtype=torch.float64, device=dev),
-                       vrp=torch.empty((B, N, 2), dtype=torch.float64, device=dev),
-                       status=torch.empty((B,), dtype=torch.int32, device=dev),
-                       iters=torch.empty((B,), dtype=torch.int32, device=dev),
-                       polished=torch.empty((B,), dtype=torch.int32, device=dev),
-                       passes=torch.empty((B,), dtype=torch.int32, device=dev))
-        pb = DcmMpcProblem(
-            _ptr(prob["xi_init"], torch.float64, (B, 2), "xi_init"),
-            _ptr(prob["omega"], torch.float64, (B, N), "omega"),
-            _ptr(prob["xi_ref"], torch.float64, (B, N + 1, 2), "xi_ref"),
-            _ptr(prob["vrp_ref"], torch.float64, (B, N, 2), "vrp_ref"),
-            _ptr(prob["A"], torch.float64, (B, N, M, 2), "A"),
-            _ptr(prob["b"], torch.float64, (B, N, M), "b"),
-            _ptr(prob["nfacets"], torch.int32, (B, N), "nfacets"))
-        so = DcmMpcSolution(
-            _ptr(out["xi"], torch.float64, (B, N + 1, 2), "xi"),
-            _ptr(out["vrp"], torch.float64, (B, N, 2), "vrp"),
-            _ptr(out["status"], torch.int32, (B,), "status"),
-            _ptr(out["iters"], torch.int32, (B,), "iters"),
-            _ptr(out["polished"], torch.int32, (B,), "polished") if "polished" in out else None,
-            _ptr(out["passes"], torch.int32, (B,), "passes") if "passes" in out else None)
-        ws = None
-        if warm is not None:
-            ws = _warm_start(warm, B, N, M)
-        lam_ptr = None
-        if lambda_out:
-            if "lam" not in out:
-                out["lam"] = torch.empty((B, N, M), dtype=torch.float64, device=dev)
-            lam_ptr = _ptr(out["lam"], torch.float64, (B, N, M), "lam")
-        self._keep = (pb, so, ws)
-        if ws is None and lam_ptr is None:
-            _check(lib().blf_dcm_mpc_solve(self._h, ctypes.byref(p), ctypes.byref(pb), B,
-                                           ctypes.byref(so), _stream(stream)))
+            out = _new(_solution_spec(B, N), prob["omega"].device)
+        pb = _problem_struct(prob, B, N, M)
+        so = _solution_struct(out, B, N)
+        ws = _warm_start(warm, B, N, M) if warm is not None else None
+        lam = _lambda_out(out, lambda_out, B, N, M)
+        if ws is None and lam is None:
+            _check(lib().blf_dcm_mpc_solve(self._h, _ref(p), _ref(pb), B, _ref(so), _stream(stream)))
         else:
-            _check(lib().blf_dcm_mpc_solve_warm(
-                self._h, ctypes.byref(p), ctypes.byref(pb),
-                ctypes.byref(ws) if ws is not None else None, B, ctypes.byref(so), lam_ptr,
-                _stream(stream)))
+            _check(lib().blf_dcm_mpc_solve_warm(self._h, _ref(p), _ref(pb), _ref(ws), B, _ref(so), lam,
+                                                _stream(stream)))
         return out
 
     def prepare_dcm_mpc_solve(self, prob, params, out, stream=None):
@@ -618,11 +655,8 @@ class Handle:
         torch = _torch()
         self.dcm_mpc_solve(prob, params, out=out, stream=stream)   # validates every argument
         B, N = prob["omega"].shape
-        M = prob["b"].shape[2]
-        pb = DcmMpcProblem(*(_vp(prob[k].data_ptr()) for k in
-                             ("xi_init", "omega", "xi_ref", "vrp_ref", "A", "b", "nfacets")))
-        so = DcmMpcSolution(*(_vp(out[k].data_ptr()) if k in out else None
-                              for k in ("xi", "vrp", "status", "iters", "polished", "passes")))
+        pb = _problem_struct(prob, B, N, prob["b"].shape[2])
+        so = _solution_struct(out, B, N)
         s = _stream(stream)
         fn, h, pp, ppb, pso = lib().blf_dcm_mpc_solve, self._h, ctypes.byref(params), ctypes.byref(pb), ctypes.byref(so)
         keep = (pb, so, params, prob, out, torch)
@@ -654,45 +688,15 @@ class Handle:
     def dcm_phase_expand(self, table, start, dt, horizon, out=None, stream=None):
         """blf_dcm_phase_expand: window arrays (A, b, nfacets, xi_ref, vrp_ref) of knots
         (start + k) dt, k = 0..horizon, from a phase table (phase_table() or the same keys)."""
-        torch = _torch()
-        B, P = table["phase_begin"].shape
-        M = table["phase_b"].shape[2]
+        tb, B, M = _phase_table_struct(table)
         N = horizon
-        dev = table["phase_begin"].device
+        window = _window_spec(B, N, M)
+        spec = {k: window[k] for k in ("A", "b", "nfacets", "xi_ref", "vrp_ref")}   # the call's order
         if out is None:
-            out = dict(A=torch.empty((B, N, M, 2), dtype=torch.float64, device=dev),
-                       b=torch.empty((B, N, M), dtype=torch.float64, device=dev),
-                       nfacets=torch.empty((B, N), dtype=torch.int32, device=dev),
-                       xi_ref=torch.empty((B, N + 1, 2), dtype=torch.float64, device=dev),
-                       vrp_ref=torch.empty((B, N, 2), dtype=torch.float64, device=dev))
-        tb = PhaseTable(P, M, _ptr(table["nphases"], torch.int32, (B,), "nphases"),
-                        _ptr(table["phase_begin"], torch.float64, (B, P), "phase_begin"),
-                        _ptr(table["phase_end"], torch.float64, (B, P), "phase_end"),
-                        _ptr(table["phase_A"], torch.float64, (B, P, M, 2), "phase_A"),
-                        _ptr(table["phase_b"], torch.float64, (B, P, M), "phase_b"),
-                        _ptr(table["phase_nf"], torch.int32, (B, P), "phase_nf"),
-                        _ptr(table["phase_ref"], torch.float64, (B, P, 2), "phase_ref"))
-        self._keep = tb
-        _check(lib().blf_dcm_phase_expand(
-            self._h, ctypes.byref(tb), int(start), float(dt), N, B,
-            _ptr(out["A"], torch.float64, (B, N, M, 2), "A"),
-            _ptr(out["b"], torch.float64, (B, N, M), "b"),
-            _ptr(out["nfacets"], torch.int32, (B, N), "nfacets"),
-            _ptr(out["xi_ref"], torch.float64, (B, N + 1, 2), "xi_ref"),
-            _ptr(out["vrp_ref"], torch.float64, (B, N, 2), "vrp_ref"), _stream(stream)))
+            out = _new(spec, table["phase_begin"].device)
+        _check(lib().blf_dcm_phase_expand(self._h, _ref(tb), int(start), float(dt), N, B, *_ptrs(out, spec),
+                                          _stream(stream)))
         return out
-
-    def _phase_table_struct(self, table):
-        torch = _torch()
-        B, P = table["phase_begin"].shape
-        M = table["phase_b"].shape[2]
-        return PhaseTable(P, M, _ptr(table["nphases"], torch.int32, (B,), "nphases"),
-                          _ptr(table["phase_begin"], torch.float64, (B, P), "phase_begin"),
-                          _ptr(table["phase_end"], torch.float64, (B, P), "phase_end"),
-                          _ptr(table["phase_A"], torch.float64, (B, P, M, 2), "phase_A"),
-                          _ptr(table["phase_b"], torch.float64, (B, P, M), "phase_b"),
-                          _ptr(table["phase_nf"], torch.int32, (B, P), "phase_nf"),
-                          _ptr(table["phase_ref"], torch.float64, (B, P, 2), "phase_ref"))
 
     def dcm_mpc_solve_phased(self, table, start, xi_init, omega, params=None, warm=None,
                              out=None, window=None, lambda_out=False, stream=None):
@@ -710,59 +714,26 @@ class Handle:
         if omega.device.type != "cuda" or omega.dtype != torch.float64 or omega.stride(1) != 1:
             raise ValueError("omega must be a float64 device tensor with unit column stride")
         ostride = omega.stride(0) if B > 1 else N
-        dev = omega.device
         if out is None:
-            out = dict(xi=torch.empty((B, N + 1, 2), dtype=torch.float64, device=dev),
-                       vrp=torch.empty((B, N, 2), dtype=torch.float64, device=dev),
-                       status=torch.empty((B,), dtype=torch.int32, device=dev),
-                       iters=torch.empty((B,), dtype=torch.int32, device=dev),
-                       polished=torch.empty((B,), dtype=torch.int32, device=dev),
-                       passes=torch.empty((B,), dtype=torch.int32, device=dev))
+            out = _new(_solution_spec(B, N), omega.device)
         if window is None:
             window = out.get("window")
         if window is None:
-            window = dict(omega=torch.empty((B, N), dtype=torch.float64, device=dev),
-                          xi_ref=torch.empty((B, N + 1, 2), dtype=torch.float64, device=dev),
-                          vrp_ref=torch.empty((B, N, 2), dtype=torch.float64, device=dev),
-                          A=torch.empty((B, N, M, 2), dtype=torch.float64, device=dev),
-                          b=torch.empty((B, N, M), dtype=torch.float64, device=dev),
-                          nfacets=torch.empty((B, N), dtype=torch.int32, device=dev))
-            out["window"] = window
-        win = DcmMpcWindow(_ptr(window["omega"], torch.float64, (B, N), "window omega"),
-                           _ptr(window["xi_ref"], torch.float64, (B, N + 1, 2), "window xi_ref"),
-                           _ptr(window["vrp_ref"], torch.float64, (B, N, 2), "window vrp_ref"),
-                           _ptr(window["A"], torch.float64, (B, N, M, 2), "window A"),
-                           _ptr(window["b"], torch.float64, (B, N, M), "window b"),
-                           _ptr(window["nfacets"], torch.int32, (B, N), "window nfacets"))
-        tb = self._phase_table_struct(table)
-        so = DcmMpcSolution(
-            _ptr(out["xi"], torch.float64, (B, N + 1, 2), "xi"),
-            _ptr(out["vrp"], torch.float64, (B, N, 2), "vrp"),
-            _ptr(out["status"], torch.int32, (B,), "status"),
-            _ptr(out["iters"], torch.int32, (B,), "iters"),
-            _ptr(out["polished"], torch.int32, (B,), "polished") if "polished" in out else None,
-            _ptr(out["passes"], torch.int32, (B,), "passes") if "passes" in out else None)
-        ws = None
-        if warm is not None:
-            ws = _warm_start(warm, B, N, M)
-        lam_ptr = None
-        if lambda_out:
-            if "lam" not in out:
-                out["lam"] = torch.empty((B, N, M), dtype=torch.float64, device=dev)
-            lam_ptr = _ptr(out["lam"], torch.float64, (B, N, M), "lam")
-        self._keep = (tb, so, ws, win)
-        args = (self._h, ctypes.byref(p), ctypes.byref(tb), int(start),
-                _ptr(xi_init, torch.float64, (B, 2), "xi_init"), _vp(omega.data_ptr()), ostride,
-                ctypes.byref(ws) if ws is not None else None, B, ctypes.byref(win), ctypes.byref(so),
-                lam_ptr)
-        _check(lib().blf_dcm_mpc_solve_phased(*args, _stream(stream)))
+            window = out["window"] = _new(_window_spec(B, N, M), omega.device)
+        win = DcmMpcWindow(*_ptrs(window, _window_spec(B, N, M), "window "))
+        tb = _phase_table_struct(table)[0]
+        so = _solution_struct(out, B, N)
+        ws = _warm_start(warm, B, N, M) if warm is not None else None
+        lam = _lambda_out(out, lambda_out, B, N, M)
+        _check(lib().blf_dcm_mpc_solve_phased(
+            self._h, _ref(p), _ref(tb), int(start), _ptr(xi_init, torch.float64, (B, 2), "xi_init"),
+            _vp(omega.data_ptr()), ostride, _ref(ws), B, _ref(win), _ref(so), lam, _stream(stream)))
         return out
 
     # --- C3 pipeline: corner sets -> polygons (device hull) -> QP arrays ---
     def assemble_constraints(self, corners, ncorners, max_facets=8, stream=None):
         """corners [B, N+1, P, 2], ncorners [B, N+1] (device) -> A [B,N,M,2], b [B,N,M],
         nfacets [B,N] for knots 0..N-1 via blf_hull2d_hrep."""
-        torch = _torch()
         B, N1, P, _ = corners.shape
         N = N1 - 1
         pts = corners[:, :N].reshape(B * N, P, 2).contiguous()
@@ -784,12 +755,11 @@ class Handle:
                            outputs=("wrench", "autonomous", "control", "regressor"), stream=None):
         """ContinuousContactModel for a batch: params [B,4] or [4] (L, W, k, b), twist [B,6],
         pose / null_pose [B,12] = (p, R row-major).  Returns the requested outputs."""
-        torch = _torch()
+        f64 = _torch().float64
         B, shared, pp, tw, ps, ns = self._contact_inputs(params, twist, pose, null_pose)
-        shapes = dict(wrench=(B, 6), autonomous=(B, 6), control=(B, 6, 6), regressor=(B, 6, 2))
-        out = {k: torch.empty(shapes[k], dtype=torch.float64, device=twist.device) for k in outputs}
-        ptrs = [ctypes.c_void_p(out[k].data_ptr()) if k in out else None
-                for k in ("wrench", "autonomous", "control", "regressor")]
+        spec = dict(wrench=((B, 6), f64), autonomous=((B, 6), f64), control=((B, 6, 6), f64),
+                    regressor=((B, 6, 2), f64))
+        out, ptrs = _requested(spec, outputs, None, twist.device)
         _check(lib().blf_contact_model_eval(self._h, pp, 1 if shared else 0, tw, ps, ns, B,
                                             *ptrs, _stream(stream)))
         return out
@@ -867,17 +837,10 @@ class Handle:
         Q = tq.shape[1]
         prm = SwingFootParams(C, 0, float(step_height), float(apex_ratio), float(landing_velocity),
                               float(landing_acceleration))
-        shapes = dict(pose=(L, Q, 12), twist=(L, Q, 6), accel=(L, Q, 6), contact_idx=(L, Q),
-                      in_contact=(L, Q))
-        res, ptrs = {}, []
-        for k in SWING_OUTPUTS:
-            if k not in outputs:
-                ptrs.append(None)
-                continue
-            dt = torch.int32 if k in ("contact_idx", "in_contact") else torch.float64
-            res[k] = out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=dt,
-                                                                             device=tq.device)
-            ptrs.append(_ptr(res[k], dt, shapes[k], k))
+        spec = dict(pose=((L, Q, 12), torch.float64), twist=((L, Q, 6), torch.float64),
+                    accel=((L, Q, 6), torch.float64), contact_idx=((L, Q), torch.int32),
+                    in_contact=((L, Q), torch.int32))
+        res, ptrs = _requested(spec, outputs, out, tq.device)
         _check(lib().blf_swing_foot_eval(
             self._h, ctypes.byref(prm), _ptr(contact_pose, torch.float64, (L, C, 12), "contact_pose"),
             _ptr(contact_time, torch.float64, (L, C, 2), "contact_time"),
@@ -891,15 +854,9 @@ class Handle:
         torch = _torch()
         S, Q = tq.shape
         R0, R1 = R0.reshape(S, 9), R1.reshape(S, 9)
-        shapes = dict(rot=(S, Q, 9), omega=(S, Q, 3), alpha=(S, Q, 3))
-        res, ptrs = {}, []
-        for k in SO3_OUTPUTS:
-            if k not in outputs:
-                ptrs.append(None)
-                continue
-            res[k] = out[k] if out is not None and k in out else torch.empty(
-                shapes[k], dtype=torch.float64, device=tq.device)
-            ptrs.append(_ptr(res[k], torch.float64, shapes[k], k))
+        spec = dict(rot=((S, Q, 9), torch.float64), omega=((S, Q, 3), torch.float64),
+                    alpha=((S, Q, 3), torch.float64))
+        res, ptrs = _requested(spec, outputs, out, tq.device)
         _check(lib().blf_so3_eval(
             self._h, _ptr(R0, torch.float64, (S, 9), "R0"), _ptr(R1, torch.float64, (S, 9), "R1"),
             _ptr(duration, torch.float64, (S,), "duration"), S, _ptr(tq, torch.float64, (S, Q), "tq"),
@@ -941,34 +898,25 @@ class Handle:
         """Upload a blf/robot.py model; returns an object keeping the device arrays alive."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
-
-        class _M:
-            pass
-        dm = _M()
-        f64 = lambda a: torch.as_tensor(a, dtype=torch.float64).contiguous().to(dev)
-        i32 = lambda a: torch.as_tensor(a, dtype=torch.int32).contiguous().to(dev)
-        dm.t = dict(parent=i32(model["parent"]), joint_origin=f64(model["joint_origin"]),
-                    joint_rot=f64(model["joint_rot"]), joint_axis=f64(model["joint_axis"]),
-                    link_mass=f64(model["link_mass"]), link_com=f64(model["link_com"]),
-                    link_inertia=f64(model["link_inertia"]), frame_link=i32(model["frame_link"]),
-                    frame_pose=f64(model["frame_pose"]))
+        kinds = dict(parent=torch.int32, joint_origin=torch.float64, joint_rot=torch.float64,
+                     joint_axis=torch.float64, link_mass=torch.float64, link_com=torch.float64,
+                     link_inertia=torch.float64, frame_link=torch.int32, frame_pose=torch.float64)
+        t = {k: _upload(model[k], dt, dev) for k, dt in kinds.items()}
         if model.get("joint_type") is not None:   # absent: every joint revolute (NULL)
             jt = torch.as_tensor(model["joint_type"], dtype=torch.int32)
             if not ((jt == 0) | (jt == 1)).all():
                 raise ValueError("joint_type: every entry must be 0 (revolute) or 1 (prismatic); merge fixed "
                                  "joints first (blf.robot.reduce_fixed_joints)")
-            dm.t["joint_type"] = i32(jt)
+            t["joint_type"] = _upload(jt, torch.int32, dev)
         c = FbModel()
         c.ndof = int(model["n"])
         c.nframes = int(len(model["frame_link"]))
-        for k, v in dm.t.items():
+        for k, v in t.items():
             setattr(c, k, _vp(v.data_ptr()))
         for i in range(3):
             c.gravity[i] = gravity[i]
         c.rho = rho
-        dm.c = c
-        dm.n = c.ndof
-        return dm
+        return _Held(c, t, n=c.ndof)
 
     def _fb_state(self, st, B, n):
         torch = _torch()
@@ -1007,10 +955,8 @@ class Handle:
         out = {k: torch.empty_like(state[k]) for k in FB_STATE_KEYS}
         B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg)
         oc = self._fb_state(out, B, n)
-        _check(lib().blf_fbd_dynamics(self._h, ctypes.byref(dm.c), ctypes.byref(st),
-                                      _ptr(torque, torch.float64, (B, n), "torque"),
-                                      ctypes.byref(ct), reg, B, ctypes.byref(oc),
-                                      _stream(stream)))
+        _check(lib().blf_fbd_dynamics(self._h, _ref(dm.c), _ref(st), _ptr(torque, torch.float64, (B, n), "torque"),
+                                      _ref(ct), reg, B, _ref(oc), _stream(stream)))
         return out
 
     def _fbd_args(self, state, contacts, mass_reg, law_batch=None):
@@ -1023,16 +969,19 @@ class Handle:
         reg = _ptr(mass_reg, torch.float64, (n + 6, n + 6), "mass_reg") if mass_reg is not None else None
         return B, n, self._fb_state(state, B, n), self._fb_contacts(contacts, B), reg
 
+    def _fbd_euler(self, fn, dm, state, law, times, contacts, mass_reg, stream, law_batch=None):
+        """The four blf_fbd_euler_integrate* calls, in place on `state`: `law` (B, n) gives the argument that
+        holds the control input, a torque pointer or a law struct's reference."""
+        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg, law_batch)
+        _check(fn(self._h, _ref(dm.c), _ref(st), law(B, n), _ref(ct), reg, B, *map(float, times), _stream(stream)))
+        return state
+
     def fbd_euler_integrate(self, dm, state, torque, t0, t1, dT, contacts=None, mass_reg=None,
                             stream=None):
         """ForwardEuler<FloatingBaseDynamicalSystem>::integrate in place on `state`."""
-        torch = _torch()
-        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg)
-        _check(lib().blf_fbd_euler_integrate(self._h, ctypes.byref(dm.c), ctypes.byref(st),
-                                             _ptr(torque, torch.float64, (B, n), "torque"),
-                                             ctypes.byref(ct), reg, B, float(t0), float(t1),
-                                             float(dT), _stream(stream)))
-        return state
+        return self._fbd_euler(lib().blf_fbd_euler_integrate, dm, state,
+                               lambda B, n: _ptr(torque, _torch().float64, (B, n), "torque"), (t0, t1, dT),
+                               contacts, mass_reg, stream)
 
     def fb_frame_state(self, dm, state, frames, pose=None, twist=None, stream=None):
         """blf_fb_frame_state: world transform pose [B,K,12] = (p, R row-major) and mixed twist
@@ -1042,14 +991,11 @@ class Handle:
         B, n = state["joint_pos"].shape
         K = frames.shape[0]
         dev = state["joint_pos"].device
-        pose = pose if pose is not None else torch.empty((B, K, 12), dtype=torch.float64, device=dev)
-        twist = twist if twist is not None else torch.empty((B, K, 6), dtype=torch.float64, device=dev)
-        _check(lib().blf_fb_frame_state(self._h, ctypes.byref(dm.c),
-                                        ctypes.byref(self._fb_state(state, B, n)), K,
-                                        _ptr(frames, torch.int32, (K,), "frames"), B,
-                                        _ptr(pose, torch.float64, (B, K, 12), "pose"),
-                                        _ptr(twist, torch.float64, (B, K, 6), "twist"),
-                                        _stream(stream)))
+        st = self._fb_state(state, B, n)
+        fp = _ptr(frames, torch.int32, (K,), "frames")
+        pose, pp = _out(pose, (B, K, 12), torch.float64, dev, "pose", optional=False)
+        twist, tp = _out(twist, (B, K, 6), torch.float64, dev, "twist", optional=False)
+        _check(lib().blf_fb_frame_state(self._h, _ref(dm.c), _ref(st), K, fp, B, pp, tp, _stream(stream)))
         return pose, twist
 
     def fb_inverse_dynamics(self, dm, state, joint_acc=None, base_acc=None, contacts=None, joint_torque=None,
@@ -1061,26 +1007,19 @@ class Handle:
         torch = _torch()
         B, n = state["joint_pos"].shape
         dev = state["joint_pos"].device
-        new = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        tau = joint_torque if joint_torque is not None else new((B, n))
-        if status is None:
-            status = torch.empty((B,), dtype=torch.int32, device=dev)
         given = base_acc is not None
-        if given:
-            six = base_wrench if base_wrench is not None else new((B, 6))
-        else:
-            six = base_acc_out if base_acc_out is not None else new((B, 6))
-        sp = _ptr(six, torch.float64, (B, 6), "base_wrench" if given else "base_acc_out")
-        _check(lib().blf_fb_inverse_dynamics(
-            self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
-            _ptr(joint_acc, torch.float64, (B, n), "joint_acc") if joint_acc is not None else None,
-            _ptr(base_acc, torch.float64, (B, 6), "base_acc") if given else None,
-            ctypes.byref(self._fb_contacts(contacts, B)), B, _ptr(tau, torch.float64, (B, n), "joint_torque"),
-            None if given else sp, sp if given else None,
-            _ptr(status, torch.int32, (B,), "status") if status is not False else None, 0, _stream(stream)))
-        out = dict(joint_torque=tau, status=status if status is not False else None)
-        out["base_wrench" if given else "base_acc"] = six
-        return out
+        six, xp = _out(base_wrench if given else base_acc_out, (B, 6), torch.float64, dev,
+                       "base_wrench" if given else "base_acc_out", optional=False)
+        st = self._fb_state(state, B, n)
+        ap = _ptr(joint_acc, torch.float64, (B, n), "joint_acc") if joint_acc is not None else None
+        bp = _ptr(base_acc, torch.float64, (B, 6), "base_acc") if given else None
+        ct = self._fb_contacts(contacts, B)
+        tau, tp = _out(joint_torque, (B, n), torch.float64, dev, "joint_torque", optional=False)
+        status, sp = _out(status, (B,), torch.int32, dev, "status")
+        _check(lib().blf_fb_inverse_dynamics(self._h, _ref(dm.c), _ref(st), ap, bp, _ref(ct), B, tp,
+                                             None if given else xp, xp if given else None, sp, 0,
+                                             _stream(stream)))
+        return {"joint_torque": tau, "status": status, "base_wrench" if given else "base_acc": six}
 
     # ---- whole-body inverse kinematics (include/blf/blf_c.h section 12) ------------------------
     def ik_tasks(self, batch, ndof, frame=None, se3_weight=None, se3_kp=None, se3_pose=None, se3_twist=None,
@@ -1094,17 +1033,8 @@ class Handle:
         with the struct (.c) and the tensors (.t) it keeps alive."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
-
-        class _T:
-            pass
-        tk = _T()
         B, n = int(batch), int(ndof)
         K = 0 if frame is None else int(len(frame))
-
-        def up(a, dtype):
-            if isinstance(a, torch.Tensor):
-                return a
-            return torch.as_tensor(a, dtype=dtype).contiguous().to(dev)
         spec = dict(frame=(frame, torch.int32, (K,)), se3_weight=(se3_weight, torch.float64, (K, 6)),
                     se3_kp=(se3_kp, torch.float64, (K, 2)), se3_pose=(se3_pose, torch.float64, (B, K, 12)),
                     se3_twist=(se3_twist, torch.float64, (B, K, 6)), com_weight=(com_weight, torch.float64, (3,)),
@@ -1114,14 +1044,13 @@ class Handle:
         c = IkTasks()
         c.nse3, c.reserved = K, 0
         c.com_kp, c.base_damping = float(com_kp), float(base_damping)
-        tk.t = {}
+        t = {}
         for k, (a, dt, shape) in spec.items():
             if a is None or (K == 0 and k in ("frame", "se3_weight", "se3_kp", "se3_pose", "se3_twist")):
                 continue
-            tk.t[k] = up(a, dt)
-            setattr(c, k, _ptr(tk.t[k], dt, shape, k))
-        tk.c, tk.batch, tk.n = c, B, n
-        return tk
+            t[k] = _on_device(a, dt, dev)
+            setattr(c, k, _ptr(t[k], dt, shape, k))
+        return _Held(c, t, batch=B, n=n)
 
     @staticmethod
     def ik_hard(se3=(), com=(False, False, False), rel_pivot_min=0.0):
@@ -1148,32 +1077,37 @@ class Handle:
         object with the struct (.c) and the tensors (.t) it keeps alive."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
-
-        class _T:
-            pass
-        lm = _T()
         n = int(len(pos_lower))
         c = IkLimits()
-        lm.t = {}
+        t = {}
         for k, a in (("pos_lower", pos_lower), ("pos_upper", pos_upper), ("klim", klim), ("vel_max", vel_max)):
             if a is None:
                 continue
-            lm.t[k] = a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=torch.float64).contiguous().to(dev)
-            setattr(c, k, _ptr(lm.t[k], torch.float64, (n,), k))
+            t[k] = _on_device(a, torch.float64, dev)
+            setattr(c, k, _ptr(t[k], torch.float64, (n,), k))
         c.sampling_time, c.max_iter, c.reserved = float(sampling_time), int(max_iter), 0
-        lm.c, lm.n = c, n
-        return lm
+        return _Held(c, t, n=n)
 
-    def _ik_limits_out(self, B, dev, iters, active):
-        """The iters [B] int32 and active [B,2] int64 outputs of the limits calls (False: not requested)."""
+    def _fb_ik(self, stem, steps, dm, state, tasks, nu, status, hard, limits, iters, active, stream):
+        """The plain, _hard and _limits entry points of blf_fb_ik_solve (steps = ()) and blf_fb_ik_integrate
+        (steps = (steps, dT)): one argument list, with the variant's structs and outputs spliced in.  Returns
+        (nu, status) and, with limits, iters and active (None for what was not requested)."""
         torch = _torch()
-        if iters is None:
-            iters = torch.zeros((B,), dtype=torch.int32, device=dev)
-        if active is None:
-            active = torch.zeros((B, 2), dtype=torch.int64, device=dev)
-        ip = _ptr(iters, torch.int32, (B,), "iters") if iters is not False else None
-        ap = _ptr(active, torch.int64, (B, 2), "active") if active is not False else None
-        return iters, active, ip, ap
+        B, n = state["joint_pos"].shape
+        dev = state["joint_pos"].device
+        res = [_out(nu, (B, 6 + n), torch.float64, dev, "nu", optional=bool(steps)),
+               _out(status, (B,), torch.int32, dev, "status")]
+        if limits is not None:
+            res += [_out(iters, (B,), torch.int32, dev, "iters", zero=True),
+                    _out(active, (B, 2), torch.int64, dev, "active", zero=True)]
+            fn, extra = stem + "_limits", (_ref(hard), _ref(limits.c))
+        elif hard is not None:
+            fn, extra = stem + "_hard", (_ref(hard),)
+        else:
+            fn, extra = stem, ()
+        _check(getattr(lib(), fn)(self._h, _ref(dm.c), _ref(self._fb_state(state, B, n)), _ref(tasks.c), *extra, B,
+                                  *steps, *(p for _, p in res), _stream(stream)))
+        return tuple(t for t, _ in res)
 
     def fb_ik_solve(self, dm, state, tasks, nu=None, status=None, stream=None, hard=None, limits=None,
                     iters=None, active=None):
@@ -1185,33 +1119,7 @@ class Handle:
         limits (an ik_limits()): blf_fb_ik_solve_limits, the joint velocities kept in section 12c's box
         (status may then be IK_LIMITS_UNRESOLVED); the call then returns (nu, status, iters [B] int32,
         active [B,2] int64: the joints that end on their lower | upper bound, a bit each)."""
-        torch = _torch()
-        B, n = state["joint_pos"].shape
-        dev = state["joint_pos"].device
-        nu = nu if nu is not None else torch.empty((B, 6 + n), dtype=torch.float64, device=dev)
-        if status is None:
-            status = torch.empty((B,), dtype=torch.int32, device=dev)
-        sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
-        if limits is not None:
-            iters, active, ip, ap = self._ik_limits_out(B, dev, iters, active)
-            _check(lib().blf_fb_ik_solve_limits(self._h, ctypes.byref(dm.c),
-                                                ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c),
-                                                ctypes.byref(hard) if hard is not None else None,
-                                                ctypes.byref(limits.c), B,
-                                                _ptr(nu, torch.float64, (B, 6 + n), "nu"), sp, ip, ap,
-                                                _stream(stream)))
-            return (nu, (status if status is not False else None), (iters if iters is not False else None),
-                    (active if active is not False else None))
-        if hard is None:
-            _check(lib().blf_fb_ik_solve(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
-                                         ctypes.byref(tasks.c), B, _ptr(nu, torch.float64, (B, 6 + n), "nu"), sp,
-                                         _stream(stream)))
-        else:
-            _check(lib().blf_fb_ik_solve_hard(self._h, ctypes.byref(dm.c),
-                                              ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c),
-                                              ctypes.byref(hard), B, _ptr(nu, torch.float64, (B, 6 + n), "nu"),
-                                              sp, _stream(stream)))
-        return nu, (status if status is not False else None)
+        return self._fb_ik("blf_fb_ik_solve", (), dm, state, tasks, nu, status, hard, limits, iters, active, stream)
 
     def fb_ik_integrate(self, dm, state, tasks, steps, dT, nu=None, status=None, stream=None, hard=None,
                         limits=None, iters=None, active=None):
@@ -1220,35 +1128,8 @@ class Handle:
         False: not requested.  hard as fb_ik_solve (blf_fb_ik_integrate_hard).  Returns (state, nu,
         status), and with limits (blf_fb_ik_integrate_limits) also iters (summed over the steps) and
         active (the last step's)."""
-        torch = _torch()
-        B, n = state["joint_pos"].shape
-        dev = state["joint_pos"].device
-        if nu is None:
-            nu = torch.empty((B, 6 + n), dtype=torch.float64, device=dev)
-        if status is None:
-            status = torch.empty((B,), dtype=torch.int32, device=dev)
-        np_ = _ptr(nu, torch.float64, (B, 6 + n), "nu") if nu is not False else None
-        sp = _ptr(status, torch.int32, (B,), "status") if status is not False else None
-        if limits is not None:
-            iters, active, ip, ap = self._ik_limits_out(B, dev, iters, active)
-            _check(lib().blf_fb_ik_integrate_limits(self._h, ctypes.byref(dm.c),
-                                                    ctypes.byref(self._fb_state(state, B, n)),
-                                                    ctypes.byref(tasks.c),
-                                                    ctypes.byref(hard) if hard is not None else None,
-                                                    ctypes.byref(limits.c), B, int(steps), float(dT), np_, sp, ip,
-                                                    ap, _stream(stream)))
-            return (state, (nu if nu is not False else None), (status if status is not False else None),
-                    (iters if iters is not False else None), (active if active is not False else None))
-        if hard is None:
-            _check(lib().blf_fb_ik_integrate(self._h, ctypes.byref(dm.c),
-                                             ctypes.byref(self._fb_state(state, B, n)), ctypes.byref(tasks.c), B,
-                                             int(steps), float(dT), np_, sp, _stream(stream)))
-        else:
-            _check(lib().blf_fb_ik_integrate_hard(self._h, ctypes.byref(dm.c),
-                                                  ctypes.byref(self._fb_state(state, B, n)),
-                                                  ctypes.byref(tasks.c), ctypes.byref(hard), B, int(steps),
-                                                  float(dT), np_, sp, _stream(stream)))
-        return state, (nu if nu is not False else None), (status if status is not False else None)
+        return (state,) + self._fb_ik("blf_fb_ik_integrate", (int(steps), float(dT)), dm, state, tasks, nu, status,
+                                      hard, limits, iters, active, stream)
 
     # ---- reference tracking (include/blf/blf_c.h section 12d) ------------------------------------
     def ik_schedule(self, batch, nse3, steps, stance_rows=0, contact=None, se3_pose=None, se3_twist=None,
@@ -1261,27 +1142,21 @@ class Handle:
         Returns an object with the struct (.c) and the tensors (.t) it keeps alive."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
-
-        class _T:
-            pass
-        sc = _T()
         B, K, T = int(batch), int(nse3), int(steps)
         c = IkSchedule()
         c.steps, c.reserved, c.stance_rows, c.reserved2 = T, 0, int(stance_rows), 0
         spec = dict(contact=(contact, torch.int32, B * K * T), se3_pose=(se3_pose, torch.float64, B * K * T * 12),
                     se3_twist=(se3_twist, torch.float64, B * K * T * 6), com_pos=(com_pos, torch.float64, B * T * 3),
                     com_vel=(com_vel, torch.float64, B * T * 3))
-        sc.t = {}
+        t = {}
         for k, (a, dt, count) in spec.items():
             if a is None or (K == 0 and k in ("contact", "se3_pose", "se3_twist")):
                 continue
-            t = a if isinstance(a, torch.Tensor) else torch.as_tensor(a, dtype=dt).contiguous().to(dev)
-            if t.numel() != count:
-                raise ValueError(f"ik_schedule: {k} has {t.numel()} elements, expected {count}")
-            sc.t[k] = t
-            setattr(c, k, _ptr(t, dt, tuple(t.shape), k))
-        sc.c, sc.batch, sc.nse3, sc.steps = c, B, K, T
-        return sc
+            t[k] = _on_device(a, dt, dev)
+            if t[k].numel() != count:
+                raise ValueError(f"ik_schedule: {k} has {t[k].numel()} elements, expected {count}")
+            setattr(c, k, _ptr(t[k], dt, tuple(t[k].shape), k))
+        return _Held(c, t, batch=B, nse3=K, steps=T)
 
     def fb_ik_track(self, dm, state, tasks, schedule, dT, hard=None, limits=None, joint_traj=None, base_traj=None,
                     nu_traj=None, status=None, fail_step=None, iters=None, active=None, stream=None):
@@ -1293,26 +1168,16 @@ class Handle:
         [B,2] int64 (None for what was not requested)."""
         torch = _torch()
         B, n = state["joint_pos"].shape
-        dev = state["joint_pos"].device
         T = schedule.steps
-        shapes = dict(joint_traj=((T, B, n), torch.float64), base_traj=((T, B, 12), torch.float64),
-                      nu_traj=((T, B, 6 + n), torch.float64), status=((B,), torch.int32),
-                      fail_step=((B,), torch.int32), iters=((B,), torch.int32), active=((B, 2), torch.int64))
+        spec = dict(joint_traj=((T, B, n), torch.float64), base_traj=((T, B, 12), torch.float64),
+                    nu_traj=((T, B, 6 + n), torch.float64), status=((B,), torch.int32),
+                    fail_step=((B,), torch.int32), iters=((B,), torch.int32), active=((B, 2), torch.int64))
         given = dict(joint_traj=joint_traj, base_traj=base_traj, nu_traj=nu_traj, status=status,
                      fail_step=fail_step, iters=iters, active=active)
-        out, ptr = {}, {}
-        for k, (shape, dt) in shapes.items():
-            a = given[k]
-            if a is None:
-                a = torch.zeros(shape, dtype=dt, device=dev)
-            out[k] = a if a is not False else None
-            ptr[k] = _ptr(a, dt, shape, k) if a is not False else None
-        _check(lib().blf_fb_ik_track(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
-                                     ctypes.byref(tasks.c), ctypes.byref(hard) if hard is not None else None,
-                                     ctypes.byref(limits.c) if limits is not None else None,
-                                     ctypes.byref(schedule.c), B, float(dT), ptr["joint_traj"], ptr["base_traj"],
-                                     ptr["nu_traj"], ptr["status"], ptr["fail_step"], ptr["iters"], ptr["active"],
-                                     _stream(stream)))
+        out, ptrs = _outs(spec, given, state["joint_pos"].device, zero=True)
+        _check(lib().blf_fb_ik_track(self._h, _ref(dm.c), _ref(self._fb_state(state, B, n)), _ref(tasks.c),
+                                     _ref(hard), _ref(limits.c if limits is not None else None),
+                                     _ref(schedule.c), B, float(dT), *ptrs, _stream(stream)))
         return dict(out, state=state)
 
     # ---- config 5: the closed loop's maps (DESIGN.md section 11) ----------------------------------
@@ -1333,7 +1198,7 @@ class Handle:
             xi = xi if xi is not None else torch.empty((B, 2), dtype=torch.float64, device=dev)
         elif xi is not None:
             raise ValueError("xi requested without omega")
-        _check(lib().blf_fb_dcm(self._h, ctypes.byref(dm.c), ctypes.byref(self._fb_state(state, B, n)),
+        _check(lib().blf_fb_dcm(self._h, _ref(dm.c), _ref(self._fb_state(state, B, n)),
                                 optr, ostride, B, _ptr(com, torch.float64, (B, 6), "com"),
                                 _ptr(xi, torch.float64, (B, 2), "xi") if xi is not None else None,
                                 _stream(stream)))
@@ -1343,20 +1208,14 @@ class Handle:
         """Upload a blf_posture_law: q_nominal [n], lean [n,2] (host arrays)."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
-
-        class _L:
-            pass
-        law = _L()
-        f64 = lambda a: torch.as_tensor(a, dtype=torch.float64).contiguous().to(dev)
-        law.t = dict(q_nominal=f64(q_nominal), lean=f64(lean))
-        n = law.t["q_nominal"].shape[0]
-        if law.t["lean"].shape != (n, 2):
+        t = dict(q_nominal=_upload(q_nominal, torch.float64, dev), lean=_upload(lean, torch.float64, dev))
+        n = t["q_nominal"].shape[0]
+        if t["lean"].shape != (n, 2):
             raise ValueError("posture law: q_nominal [n] and lean [n,2]")
         c = PostureLaw()
         c.ndof = n
-        c.q_nominal, c.lean = _vp(law.t["q_nominal"].data_ptr()), _vp(law.t["lean"].data_ptr())
-        law.c = c
-        return law
+        c.q_nominal, c.lean = _vp(t["q_nominal"].data_ptr()), _vp(t["lean"].data_ptr())
+        return _Held(c, t)
 
     def posture_reference(self, law, com, vrp, q_ref=None, stream=None):
         """blf_dcm_posture_reference: joint references [B,n] from the plan's first VRP (vrp
@@ -1376,24 +1235,23 @@ class Handle:
         """Device copies of the impedance gains kp, kd [n] (host arrays)."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
-        f64 = lambda a: torch.as_tensor(a, dtype=torch.float64).contiguous().to(dev)
-        return dict(kp=f64(kp), kd=f64(kd))
+        return dict(kp=_upload(kp, torch.float64, dev), kd=_upload(kd, torch.float64, dev))
 
     def fbd_euler_integrate_impedance(self, dm, state, impedance, q_ref, t0, t1, dT, contacts=None,
                                       mass_reg=None, stream=None):
         """blf_fbd_euler_integrate_impedance in place on `state`: the control input of every
         Euler step is tau = kp (q_ref - q) - kd qdot (impedance: joint_impedance())."""
         torch = _torch()
-        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg)
         imp = JointImpedance()
-        imp.ndof = n
-        imp.kp = _ptr(impedance["kp"], torch.float64, (n,), "kp")
-        imp.kd = _ptr(impedance["kd"], torch.float64, (n,), "kd")
-        imp.q_ref = _ptr(q_ref, torch.float64, (B, n), "q_ref")
-        args = (self._h, ctypes.byref(dm.c), ctypes.byref(st), ctypes.byref(imp), ctypes.byref(ct), reg, B,
-                float(t0), float(t1), float(dT))
-        _check(lib().blf_fbd_euler_integrate_impedance(*args, _stream(stream)))
-        return state
+
+        def law(B, n):
+            imp.ndof = n
+            imp.kp = _ptr(impedance["kp"], torch.float64, (n,), "kp")
+            imp.kd = _ptr(impedance["kd"], torch.float64, (n,), "kd")
+            imp.q_ref = _ptr(q_ref, torch.float64, (B, n), "q_ref")
+            return ctypes.byref(imp)
+        return self._fbd_euler(lib().blf_fbd_euler_integrate_impedance, dm, state, law, (t0, t1, dT), contacts,
+                               mass_reg, stream)
 
     def joint_impedance_traj(self, impedance, q_ref, steps_per_slice, qd_ref=None, qd_offset=0, q_bias=None):
         """A blf_joint_impedance_traj: impedance (joint_impedance()), q_ref [T,B,n] (fb_ik_track's
@@ -1401,17 +1259,13 @@ class Handle:
         (fb_ik_track's nu_traj with qd_offset = 6), q_bias [B,n] or None.  Returns an object with the
         struct (.c) and the tensors (.t) it keeps alive."""
         torch = _torch()
-
-        class _T:
-            pass
-        it = _T()
         T, B, n = q_ref.shape
         c = JointImpedanceTraj()
         c.ndof, c.slices, c.steps_per_slice, c.reserved = n, T, int(steps_per_slice), 0
         c.kp = _ptr(impedance["kp"], torch.float64, (n,), "kp")
         c.kd = _ptr(impedance["kd"], torch.float64, (n,), "kd")
         c.q_ref = _ptr(q_ref, torch.float64, (T, B, n), "q_ref")
-        it.t = dict(kp=impedance["kp"], kd=impedance["kd"], q_ref=q_ref, qd_ref=qd_ref, q_bias=q_bias)
+        t = dict(kp=impedance["kp"], kd=impedance["kd"], q_ref=q_ref, qd_ref=qd_ref, q_bias=q_bias)
         if qd_ref is not None:
             w = qd_ref.shape[-1]
             _ptr(qd_ref, torch.float64, (T, B, w), "qd_ref")
@@ -1420,19 +1274,15 @@ class Handle:
             c.qd_ref, c.qd_stride = _vp(qd_ref.data_ptr() + 8 * int(qd_offset)), w
         if q_bias is not None:
             c.q_bias = _ptr(q_bias, torch.float64, (B, n), "q_bias")
-        it.c, it.batch = c, B
-        return it
+        return _Held(c, t, batch=B)
 
     def fbd_euler_integrate_impedance_traj(self, dm, state, traj, t0, t1, dT, contacts=None, mass_reg=None,
                                            stream=None):
         """blf_fbd_euler_integrate_impedance_traj in place on `state`: integration step i tracks slice
         min(i // steps_per_slice, T - 1) of traj (joint_impedance_traj()),
         tau = kp (q_ref + q_bias - q) - kd (qdot - qd_ref)."""
-        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg, traj.batch)
-        args = (self._h, ctypes.byref(dm.c), ctypes.byref(st), ctypes.byref(traj.c), ctypes.byref(ct), reg, B,
-                float(t0), float(t1), float(dT))
-        _check(lib().blf_fbd_euler_integrate_impedance_traj(*args, _stream(stream)))
-        return state
+        return self._fbd_euler(lib().blf_fbd_euler_integrate_impedance_traj, dm, state,
+                               lambda B, n: ctypes.byref(traj.c), (t0, t1, dT), contacts, mass_reg, stream, traj.batch)
 
     def computed_torque_traj(self, kp, kd, q_ref, steps_per_slice, qd_ref=None, qd_offset=0, qdd_ref=None,
                              q_bias=None, tau_max=None, qdd_offset=0, tau_last=None):
@@ -1442,23 +1292,19 @@ class Handle:
         [n], finite and > 0) or None, tau_last [B,n] (True allocates) or None.  Returns an object with the
         struct (.c) and the tensors (.t) it keeps alive."""
         torch = _torch()
-
-        class _T:
-            pass
-        it = _T()
         T, B, n = q_ref.shape
         dev = q_ref.device
 
-        def vec(a, name):
+        def vec(a):
             if isinstance(a, torch.Tensor) and a.is_cuda:
                 return a
             v = torch.as_tensor(a, dtype=torch.float64).reshape(-1)
-            return (v.expand(n) if v.numel() == 1 else v).contiguous().to(dev)
+            return _upload(v.expand(n) if v.numel() == 1 else v, torch.float64, dev)
         c = ComputedTorqueTraj()
         c.ndof, c.slices, c.steps_per_slice, c.reserved = n, T, int(steps_per_slice), 0
-        it.t = dict(kp=vec(kp, "kp"), kd=vec(kd, "kd"), q_ref=q_ref, qd_ref=qd_ref, qdd_ref=qdd_ref, q_bias=q_bias)
-        c.kp = _ptr(it.t["kp"], torch.float64, (n,), "kp")
-        c.kd = _ptr(it.t["kd"], torch.float64, (n,), "kd")
+        t = dict(kp=vec(kp), kd=vec(kd), q_ref=q_ref, qd_ref=qd_ref, qdd_ref=qdd_ref, q_bias=q_bias)
+        c.kp = _ptr(t["kp"], torch.float64, (n,), "kp")
+        c.kd = _ptr(t["kd"], torch.float64, (n,), "kd")
         c.q_ref = _ptr(q_ref, torch.float64, (T, B, n), "q_ref")
         for name, ref, off in (("qd", qd_ref, qd_offset), ("qdd", qdd_ref, qdd_offset)):
             if ref is None:
@@ -1476,26 +1322,22 @@ class Handle:
                 tm = torch.as_tensor(tau_max, dtype=torch.float64)
                 if not bool((torch.isfinite(tm) & (tm > 0)).all()):
                     raise ValueError("tau_max: every entry must be finite and > 0")
-            it.t["tau_max"] = vec(tau_max, "tau_max")
-            c.tau_max = _ptr(it.t["tau_max"], torch.float64, (n,), "tau_max")
+            t["tau_max"] = vec(tau_max)
+            c.tau_max = _ptr(t["tau_max"], torch.float64, (n,), "tau_max")
         if tau_last is True:
             tau_last = torch.empty((B, n), dtype=torch.float64, device=dev)
         if tau_last is not None:
             c.tau_last = _ptr(tau_last, torch.float64, (B, n), "tau_last")
-        it.t["tau_last"] = it.tau_last = tau_last
-        it.c, it.batch = c, B
-        return it
+        t["tau_last"] = tau_last
+        return _Held(c, t, batch=B, tau_last=tau_last)
 
     def fbd_euler_integrate_computed_torque_traj(self, dm, state, law, t0, t1, dT, contacts=None, mass_reg=None,
                                                  stream=None):
         """blf_fbd_euler_integrate_computed_torque_traj in place on `state`: before every step the torque
         is the free-base inverse dynamics of sdd = qdd_ref + kp (q_ref + q_bias - q) + kd (qd_ref - qdot),
         clamped to tau_max, then the forward step (law: computed_torque_traj()).  mass_reg is refused."""
-        B, n, st, ct, reg = self._fbd_args(state, contacts, mass_reg, law.batch)
-        args = (self._h, ctypes.byref(dm.c), ctypes.byref(st), ctypes.byref(law.c), ctypes.byref(ct), reg, B,
-                float(t0), float(t1), float(dT))
-        _check(lib().blf_fbd_euler_integrate_computed_torque_traj(*args, _stream(stream)))
-        return state
+        return self._fbd_euler(lib().blf_fbd_euler_integrate_computed_torque_traj, dm, state,
+                               lambda B, n: ctypes.byref(law.c), (t0, t1, dT), contacts, mass_reg, stream, law.batch)
 
     def dcm_com_reference(self, xi0, vrp, omega, z_ref, c_ref, steps, dT, column=0, com_pos=None, com_vel=None,
                           xi_end=None, stream=None):
@@ -1511,16 +1353,11 @@ class Handle:
         _ptr(omega, torch.float64, (B, K), "omega")
         if not 0 <= column < K:
             raise ValueError(f"omega column {column} outside [0, {K})")
-        new = lambda shape: torch.empty(shape, dtype=torch.float64, device=dev)
-        com_pos = com_pos if com_pos is not None else new((B, max(T, 0), 3))
-        com_vel = com_vel if com_vel is not None else new((B, max(T, 0), 3))
-        if xi_end is None:
-            xi_end = new((B, 2))
-        shp = (B, max(T, 0), 3)
-        _check(lib().blf_dcm_com_reference(
-            self._h, _ptr(xi0, torch.float64, (B, 2), "xi0"), _ptr(vrp, torch.float64, (B, N, 2), "vrp"), 2 * N,
-            _vp(omega.data_ptr() + 8 * column), K, _ptr(z_ref, torch.float64, (B,), "z_ref"),
-            _ptr(c_ref, torch.float64, (B, 2), "c_ref"), T, float(dT), B,
-            _ptr(com_pos, torch.float64, shp, "com_pos"), _ptr(com_vel, torch.float64, shp, "com_vel"),
-            _ptr(xi_end, torch.float64, (B, 2), "xi_end") if xi_end is not False else None, _stream(stream)))
-        return com_pos, com_vel, (xi_end if xi_end is not False else None)
+        args = (self._h, _ptr(xi0, torch.float64, (B, 2), "xi0"), _ptr(vrp, torch.float64, (B, N, 2), "vrp"), 2 * N,
+                _vp(omega.data_ptr() + 8 * column), K, _ptr(z_ref, torch.float64, (B,), "z_ref"),
+                _ptr(c_ref, torch.float64, (B, 2), "c_ref"), T, float(dT), B)
+        com_pos, pp = _out(com_pos, (B, max(T, 0), 3), torch.float64, dev, "com_pos", optional=False)
+        com_vel, vp = _out(com_vel, (B, max(T, 0), 3), torch.float64, dev, "com_vel", optional=False)
+        xi_end, ep = _out(xi_end, (B, 2), torch.float64, dev, "xi_end")
+        _check(lib().blf_dcm_com_reference(*args, pp, vp, ep, _stream(stream)))
+        return com_pos, com_vel, xi_end

@@ -17,48 +17,13 @@ FAKE_ARRAY = 8
 MODEL_ARRAYS = ("parent", "joint_origin", "joint_rot", "joint_axis", "link_mass", "link_com", "link_inertia")
 
 P, I32, I64, F64 = "ptr", "i32", "i64", "f64"
-_TIMES = (("initial_time", F64), ("final_time", F64), ("dT", F64))
-_HEAD = (("handle", P), ("model", native.FbModel), ("state", native.FbState))
-_IK = _HEAD + (("tasks", native.IkTasks),)
-_NU = (("nu", P), ("status", P))
-_STEPS = (("steps", I32), ("dT", F64))
-_SETS = (("iters", P), ("active", P))
+_SCALARS = {ctypes.c_void_p: P, ctypes.c_int32: I32, ctypes.c_int64: I64, ctypes.c_double: F64}
 
-# argument names and kinds in the order of the C declarations
-SIGNATURES = {
-    "blf_fbd_dynamics": _HEAD + (("joint_torque", P), ("contacts", native.FbContacts), ("mass_reg", P),
-                                 ("batch", I64), ("out", native.FbState), ("stream", P)),
-    "blf_fbd_euler_integrate": _HEAD + (("joint_torque", P), ("contacts", native.FbContacts), ("mass_reg", P),
-                                        ("batch", I64)) + _TIMES + (("stream", P),),
-    "blf_fbd_euler_integrate_impedance": _HEAD + (("impedance", native.JointImpedance),
-                                                  ("contacts", native.FbContacts), ("mass_reg", P),
-                                                  ("batch", I64)) + _TIMES + (("stream", P),),
-    "blf_fbd_euler_integrate_impedance_traj": _HEAD + (("impedance", native.JointImpedanceTraj),
-                                                       ("contacts", native.FbContacts), ("mass_reg", P),
-                                                       ("batch", I64)) + _TIMES + (("stream", P),),
-    "blf_fbd_euler_integrate_computed_torque_traj": _HEAD + (("law", native.ComputedTorqueTraj),
-                                                             ("contacts", native.FbContacts), ("mass_reg", P),
-                                                             ("batch", I64)) + _TIMES + (("stream", P),),
-    "blf_fb_inverse_dynamics": _HEAD + (("joint_acc", P), ("base_acc", P), ("contacts", native.FbContacts),
-                                        ("batch", I64), ("joint_torque", P), ("base_acc_out", P),
-                                        ("base_wrench", P), ("status", P), ("reserved", I32), ("stream", P)),
-    "blf_fb_dcm": _HEAD + (("omega0", P), ("omega0_stride", I64), ("batch", I64), ("com", P), ("xi", P),
-                           ("stream", P)),
-    "blf_fb_frame_state": _HEAD + (("nframes", I32), ("frames", P), ("batch", I64), ("pose", P), ("twist", P),
-                                   ("stream", P)),
-    "blf_fb_ik_solve": _IK + (("batch", I64),) + _NU + (("stream", P),),
-    "blf_fb_ik_integrate": _IK + (("batch", I64),) + _STEPS + _NU + (("stream", P),),
-    "blf_fb_ik_solve_hard": _IK + (("hard", native.IkHard), ("batch", I64)) + _NU + (("stream", P),),
-    "blf_fb_ik_integrate_hard": _IK + (("hard", native.IkHard), ("batch", I64)) + _STEPS + _NU + (("stream", P),),
-    "blf_fb_ik_solve_limits": _IK + (("hard", native.IkHard), ("limits", native.IkLimits), ("batch", I64)) + _NU
-                              + _SETS + (("stream", P),),
-    "blf_fb_ik_integrate_limits": _IK + (("hard", native.IkHard), ("limits", native.IkLimits), ("batch", I64))
-                                  + _STEPS + _NU + _SETS + (("stream", P),),
-    "blf_fb_ik_track": _IK + (("hard", native.IkHard), ("limits", native.IkLimits),
-                              ("schedule", native.IkSchedule), ("batch", I64), ("dT", F64), ("joint_traj", P),
-                              ("base_traj", P), ("nu_traj", P), ("status", P), ("fail_step", P)) + _SETS
-                       + (("stream", P),),
-}
+# argument names and kinds (a scalar kind, or the struct class a pointer argument points to) of the
+# floating-base entry points, those that take a blf_fb_model, from the binding's table of the C declarations
+SIGNATURES = {entry: tuple((name, _SCALARS.get(t) or t._type_) for name, t in args)
+              for entry, (_, args) in native.SIGNATURES.items()
+              if ("model", ctypes.POINTER(native.FbModel)) in args}
 ENTRY_POINTS = tuple(SIGNATURES)
 
 # the accepted call: scalar arguments and struct members that are not zero / null

@@ -46,9 +46,6 @@ def test_step_schedule_matches_reference_loop():
     from blf import native
     L = native.lib()
     f = L.blf_step_schedule
-    f.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32),
-                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-    f.restype = ctypes.c_int32
     it, dl, tl = ctypes.c_int32(), ctypes.c_double(), ctypes.c_double()
     for t0, T, dT in ((0.0, 0.02, 0.001), (0.0, 0.019, 0.001), (0.3, 1.0, 0.07), (0.0, 0.0005, 0.001),
                       (1.0, 1.25, 0.1), (-2.0, 3.0, 0.3)):
