@@ -221,6 +221,21 @@ __device__ __forceinline__ void assume_pad(int N)
     if (KPL == 2 && TR != kTreeDpp) __builtin_assume((TR == kTreePad) == (N <= 2 * kWave - 2));
 }
 
+// The float passes of the knot-pair kernels (the headline batch's float search) take forms of
+// their own, bit-identical to the general ones:
+//   * the zero element / identity of a lane without the knot is selected by ownership, not filled
+//     and then overwritten inside an `if (k < N)` region (rc_knot, as_solve): the compiler lowers
+//     the regions to constant fills plus a copy of every value out of them, 79 v_mov of a pass;
+//   * pass invariants are carried across the pass loop: the ownership selects, the weights as
+//     vector operands (carry_in_vgpr), the solve's P h products.
+// Every other instance keeps the general form.  The fp64 passes have no registers to carry
+// anything in (carried, the bench instance spills) and their 64-bit selects cost what the moves
+// cost; one knot per lane is a lone wavefront bound by its dependency chain, where a select
+// between a knot's arithmetic and its scan is one more link: the warm window, the three-contact
+// window and the single solve measured 1-3 % slower with these forms.
+template <class T, int KPL>
+constexpr bool kPairFloat = sizeof(T) == 4 && KPL == 2;
+
 // One level L of the DPP tree for the affine scans: (g, e) <- (g, e) o the element of the level's
 // source lane, on the lanes that have one (tree_has); the others keep their element.
 template <int L, bool FWD, class T>
@@ -404,10 +419,15 @@ __device__ __forceinline__ void as_residuals(AKnotT<T>& K, const PT<T>& P, bool 
 
 // Riccati sweep (oracle riccati_sweep_pairs; KPL = 1: riccati_sweep on one wavefront): leaves
 // P_{k+1} in K; false on a lane where some (I + G H) or (I + G P) is not positive definite.
-template <class T>
+template <bool SEL, class T>
 __device__ __forceinline__ void rc_knot(RcT<T>& e, bool own, T al, const T (&E)[3], const PT<T>& P)
 {
-    if (own) {
+    if constexpr (SEL) {   // kPairFloat: three selects (the callers' E is zero on a lane without the knot)
+        const T a = own ? al : T(1);
+        e.a0 = a; e.a1 = T(0); e.a2 = T(0); e.a3 = a;
+        e.g0 = E[0]; e.g1 = E[1]; e.g2 = E[2];
+        e.h0 = own ? P.Qw0 : T(0); e.h1 = T(0); e.h2 = own ? P.Qw1 : T(0);
+    } else if (own) {
         e.a0 = al; e.a1 = T(0); e.a2 = T(0); e.a3 = al;
         e.g0 = E[0]; e.g1 = E[1]; e.g2 = E[2];
         e.h0 = P.Qw0; e.h1 = T(0); e.h2 = P.Qw1;
@@ -424,10 +444,10 @@ __device__ __forceinline__ bool as_riccati(AKnotT<T> (&K)[KPL], const PT<T>& P, 
 {
     bool ok = true;
     RcT<T> e;
-    rc_knot(e, KPL * lane < N, K[0].al, E[0], P);
+    rc_knot<kPairFloat<T, KPL>>(e, KPL * lane < N, K[0].al, E[0], P);
     if constexpr (KPL == 2) {
         RcT<T> e1;
-        rc_knot(e1, KPL * lane + 1 < N, K[1].al, E[1], P);
+        rc_knot<kPairFloat<T, KPL>>(e1, KPL * lane + 1 < N, K[1].al, E[1], P);
         ok = rc_combine(e, e1) && ok;
     }
     const int ln = opaque(lane);
@@ -478,7 +498,7 @@ __device__ __forceinline__ bool as_riccati(AKnotT<T> (&K)[KPL], const PT<T>& P, 
     K[L].P11 = Pn11;
     if constexpr (KPL == 2) {   // P_{2l+1} = f_{2l+1}(P_{2l+2}), the first knot's P_{k+1}
         RcT<T> e1;
-        rc_knot(e1, KPL * lane + 1 < N, K[1].al, E[1], P);
+        rc_knot<kPairFloat<T, KPL>>(e1, KPL * lane + 1 < N, K[1].al, E[1], P);
         T o00, o01, o11;
         ok = rc_apply(e1, Pn00, Pn01, Pn11, o00, o01, o11) && ok;
         K[0].P00 = o00;
@@ -501,12 +521,19 @@ template <int KPL, int TR, class T>
 __device__ __forceinline__ void as_solve(const AKnotT<T> (&K)[KPL], const T (&g)[KPL][2], int N, int lane,
                                          T (&dr)[KPL][2], T (&dx)[KPL][2], T (&vn)[KPL][2])
 {
+    // kPairFloat: every lane computes the knot's values (registers only) and the scanned ones are
+    // selected by ownership; y and k need no zero (k of a lane without the knot reaches only its
+    // dr, which no caller reads); m = P h and al be of the last block are then carried from here.
+    constexpr bool kSel = kPairFloat<T, KPL>;
     T G[KPL][4], c[KPL][2], y[KPL][2];
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
-        G[j][0] = G[j][1] = G[j][2] = G[j][3] = T(0);
-        c[j][0] = c[j][1] = y[j][0] = y[j][1] = T(0);
-        if (KPL * lane + j < N) {
+        const bool own = KPL * lane + j < N;
+        if constexpr (!kSel) {
+            G[j][0] = G[j][1] = G[j][2] = G[j][3] = T(0);
+            c[j][0] = c[j][1] = y[j][0] = y[j][1] = T(0);
+        }
+        if (kSel || own) {
             const AKnotT<T>& Kj = K[j];
             const T b2 = Kj.be * Kj.be;
             const T ab = Kj.al * Kj.be;
@@ -525,6 +552,12 @@ __device__ __forceinline__ void as_solve(const AKnotT<T> (&K)[KPL], const T (&g)
             c[j][0] = FD3(G[j][0], y[j][0], G[j][1], y[j][1], ab * Mg0);
             c[j][1] = FD3(G[j][2], y[j][0], G[j][3], y[j][1], ab * Mg1);
         }
+        if constexpr (kSel) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) G[j][i] = own ? G[j][i] : T(0);
+            c[j][0] = own ? c[j][0] : T(0);
+            c[j][1] = own ? c[j][1] : T(0);
+        }
     }
     T Gt[KPL][4];
 #pragma unroll
@@ -535,8 +568,9 @@ __device__ __forceinline__ void as_solve(const AKnotT<T> (&K)[KPL], const T (&g)
     T k[KPL][2], f[KPL][2];
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
-        k[j][0] = k[j][1] = f[j][0] = f[j][1] = T(0);
-        if (KPL * lane + j < N) {
+        const bool own = KPL * lane + j < N;
+        if constexpr (!kSel) k[j][0] = k[j][1] = f[j][0] = f[j][1] = T(0);
+        if (kSel || own) {
             const AKnotT<T>& Kj = K[j];
             const T t0 = y[j][0] + vn[j][0];
             const T t1 = y[j][1] + vn[j][1];
@@ -546,6 +580,10 @@ __device__ __forceinline__ void as_solve(const AKnotT<T> (&K)[KPL], const T (&g)
             k[j][1] = -FD2(Kj.h01, hu0, Kj.h11, hu1);
             f[j][0] = fma(-Kj.be, k[j][0], Kj.d0);
             f[j][1] = fma(-Kj.be, k[j][1], Kj.d1);
+        }
+        if constexpr (kSel) {
+            f[j][0] = own ? f[j][0] : T(0);
+            f[j][1] = own ? f[j][1] : T(0);
         }
     }
     T xk[KPL][2];
@@ -1323,17 +1361,38 @@ __device__ __forceinline__ int as_cand(const AKnotT<T>& K)
     return ((K.gm & ~K.drop) | K.add) & ((1 << K.m) - 1);
 }
 
+// The parameters as the pass loop reads them: kPairFloat moves the weights its selects read to
+// vector registers once (14 v_mov from SGPRs per pass otherwise) and returns that copy; any other
+// instance gets the caller's struct itself.
+template <int KPL, class T>
+__device__ __forceinline__ decltype(auto) pass_params(const PT<T>& P)
+{
+    if constexpr (kPairFloat<T, KPL>) {
+        PT<T> V = P;
+        carry_in_vgpr(V.Rw0);
+        carry_in_vgpr(V.Rw1);
+        carry_in_vgpr(V.Qw0);
+        carry_in_vgpr(V.Qw1);
+        carry_in_vgpr(V.Pw0);
+        carry_in_vgpr(V.Pw1);
+        return V;
+    } else {
+        return (P);
+    }
+}
+
 // handover >= 0 (the fp32 search): a failed pass that changed the candidate sets of at most
 // `handover` knots ends the search, its next candidate sets going to the fp64 passes instead of
 // another float pass (oracle passes32): the last float pass before the
 // certifying one changes a few knots, and the fp64 passes certify that set.  -1: never.
 // rr: the rows in registers for the certificate's feasibility scan (RegRows, float), or NoRows.
 template <int KPL, int TR, class T, class RS, class RR>
-__device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& P, const RS& R, int NH, int N,
+__device__ __forceinline__ bool as_passes(AKnotT<T> (&K)[KPL], const PT<T>& Pin, const RS& R, int NH, int N,
                                           int lane, T xi00, T xi01, int (&pk)[KPL],
                                           T (&pl)[KPL][2], int count_slot, int sb, int handover, int& npass,
                                           const RR& rr)
 {
+    decltype(auto) P = pass_params<KPL>(Pin);
     T xk[KPL][2];
     as_xi_prev<KPL, T>(K, lane, xi00, xi01, xk);
     bool certified = false;

@@ -180,6 +180,11 @@ __device__ __forceinline__ int opaque(int k)
     return k;
 }
 
+// A wave-uniform value moved to a vector register once, for a loop that has registers free and
+// reads it where an instruction takes no second scalar operand (a select whose mask is scalar
+// already): otherwise a v_mov from the SGPR at every such use.
+__device__ __forceinline__ void carry_in_vgpr(float& x) { asm volatile("" : "+v"(x)); }
+
 // The facet-count predicates (i < m_k per lane, i < mmax per QP) never change during a solve, so
 // the compiler would hoist all 8 of each out of the IPM loop as 64-bit lane masks and spill them
 // to VGPR lanes (46 SGPRs; every use then costs two v_readlane).  Each facet loop reads the counts
