@@ -254,6 +254,12 @@ SIGNATURES = {
         joint_torque=_vp, base_acc_out=_vp, base_wrench=_vp, status=_vp, reserved=_i32, stream=_vp),
     "blf_fbd_euler_integrate_computed_torque_traj": _sig(**_FB, law=_P(ComputedTorqueTraj),
         contacts=_P(FbContacts), mass_reg=_vp, batch=_i64, **_TIMES, stream=_vp),
+    "blf_schmitt_trigger_advance": _sig(handle=_vp, ncontacts=_i32, params=_vp, shared_params=_i32, time=_vp,
+        value=_vp, steps=_i32, state=_vp, timers=_vp, state_out=_vp, batch=_i64, stream=_vp),
+    "blf_legged_odometry_advance": _sig(handle=_vp, fb_model=_P(FbModel), ncontacts=_i32, frames=_vp, params=_vp,
+        shared_params=_i32, time=_vp, joint_pos=_vp, joint_vel=_vp, normal_force=_vp, steps=_i32, trig_state=_vp,
+        trig_timers=_vp, fixed_frame=_vp, fixed_pose=_vp, base_pos=_vp, base_rot=_vp, base_vel=_vp,
+        contact_out=_vp, fixed_out=_vp, status=_vp, batch=_i64, reserved=_i32, stream=_vp),
 }
 EXPORTED = list(SIGNATURES)
 
@@ -823,6 +829,71 @@ class Handle:
             _ptr(state, torch.float64, (B, 2), "state"),
             _ptr(covariance, torch.float64, (B, 2, 2), "covariance"), B, _stream(stream)))
         return state, covariance
+
+    # ---- Contacts::SchmittTriggerDetector / Estimators::LeggedOdometry, batched (section 13) ----
+    @staticmethod
+    def _trigger_params(params, K):
+        """The trigger parameters as the HOST array the library reads: (array kept alive, shared, pointer)."""
+        import numpy as np
+        if isinstance(params, _torch().Tensor):
+            params = params.detach().cpu().numpy()
+        p = np.ascontiguousarray(params, dtype=np.float64)
+        if p.shape not in ((4,), (K, 4)):
+            raise ValueError(f"params has shape {p.shape}, expected (4,) or ({K}, 4)")
+        return p, 1 if p.ndim == 1 else 0, _vp(p.ctypes.data)
+
+    def schmitt_trigger_advance(self, params, time, value, state, timers, state_out=None, stream=None):
+        """T samples of B x K Schmitt triggers (blf_schmitt_trigger_advance): params [4] (shared) or [K,4] =
+        (on_threshold, off_threshold, switch_on_after, switch_off_after), a host array; time [T], value
+        [T,B,K] (or [B,K] with time a scalar tensor [1]: one sample), state [B,K] int32, timers [B,K,2].
+        Updates state and timers in place; returns (state, timers, state_out [T,B,K] int32, or None when
+        state_out=False)."""
+        torch = _torch()
+        if value.dim() == 2:
+            value = value.unsqueeze(0)
+        T, B, K = value.shape
+        p, shared, pp = self._trigger_params(params, K)
+        out, op = _out(state_out, (T, B, K), torch.int32, value.device, "state_out")
+        _check(lib().blf_schmitt_trigger_advance(
+            self._h, K, pp, shared, _ptr(time, torch.float64, (T,), "time"),
+            _ptr(value, torch.float64, (T, B, K), "value"), T, _ptr(state, torch.int32, (B, K), "state"),
+            _ptr(timers, torch.float64, (B, K, 2), "timers"), op, B, _stream(stream)))
+        return state, timers, out
+
+    ODOMETRY_OUTPUTS = ("base_pos", "base_rot", "base_vel", "contact_out", "fixed_out", "status")
+
+    def legged_odometry(self, dm, frames, params, time, joint_pos, joint_vel, normal_force, est,
+                        outputs=ODOMETRY_OUTPUTS, out=None, stream=None):
+        """T steps of B legged-odometry estimators in one launch (blf_legged_odometry_advance).  dm: fb_model's
+        result; frames [K] int32 device tensor (the model's frame of each contact slot); params as in
+        schmitt_trigger_advance; time [T], joint_pos [T,B,n], joint_vel [T,B,n] or None (zero), normal_force
+        [T,B,K].  est: the estimator state, updated in place: dict(trig_state [B,K] int32, trig_timers [B,K,2],
+        fixed_frame [B] int32, fixed_pose [B,12]) -- blf.robot.odometry_init builds it.  Returns a dict of the
+        requested `outputs` (into out[name] where given): base_pos [T,B,3], base_rot [T,B,3,3], base_vel
+        [T,B,6], contact_out [T,B,K] int32, fixed_out [T,B] int32, status [B] int32."""
+        torch = _torch()
+        T, B, n = joint_pos.shape
+        if n != dm.n:
+            raise ValueError(f"joint_pos has {n} joints, the model {dm.n}")
+        K = frames.shape[0]
+        dev = joint_pos.device
+        p, shared, pp = self._trigger_params(params, K)
+        i32, f64 = torch.int32, torch.float64
+        spec = dict(base_pos=((T, B, 3), f64), base_rot=((T, B, 3, 3), f64), base_vel=((T, B, 6), f64),
+                    contact_out=((T, B, K), i32), fixed_out=((T, B), i32), status=((B,), i32))
+        unknown = set(outputs) - set(spec)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        res, optrs = _requested(spec, outputs, out, dev)
+        state_spec = dict(trig_state=((B, K), i32), trig_timers=((B, K, 2), f64), fixed_frame=((B,), i32),
+                          fixed_pose=((B, 12), f64))
+        _check(lib().blf_legged_odometry_advance(
+            self._h, _ref(dm.c), K, _ptr(frames, i32, (K,), "frames"), pp, shared, _ptr(time, f64, (T,), "time"),
+            _ptr(joint_pos, f64, (T, B, n), "joint_pos"),
+            _ptr(joint_vel, f64, (T, B, n), "joint_vel") if joint_vel is not None else None,
+            _ptr(normal_force, f64, (T, B, K), "normal_force"), T, *_ptrs(est, state_spec, "est."), *optrs, B, 0,
+            _stream(stream)))
+        return res
 
     # ---- Planners::SwingFootPlanner / SO3Planner, batched ------------------------------------
     def swing_foot_eval(self, contact_pose, contact_time, ncontacts, tq, step_height=0.05,

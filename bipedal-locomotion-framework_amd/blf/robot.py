@@ -254,6 +254,29 @@ def sole_null_poses(model, states):
     return null
 
 
+def odometry_init(model, states, frames, fixed_slot, handle=None):
+    """The estimator state of Handle.legged_odometry for robots whose true state is known (include/blf/blf_c.h
+    section 13): zeroed trigger states and timers, fixed_frame = fixed_slot (an int, or one slot per robot) and
+    fixed_pose = that slot's frame's world transform at `states`, through Handle.fb_frame_state.  model: a model
+    of this module or Handle.fb_model's result; states: the device tensors of the floating-base calls; frames
+    [K] int32 device tensor; handle: the native.Handle to evaluate on (one on the states' device if None).
+    Returns dict(trig_state [B,K] int32, trig_timers [B,K,2], fixed_frame [B] int32, fixed_pose [B,12])."""
+    import torch
+    from . import native
+    dev = states["joint_pos"].device
+    h = handle if handle is not None else native.Handle(dev.index or 0)
+    dm = h.fb_model(model) if isinstance(model, dict) else model
+    B, K = states["joint_pos"].shape[0], frames.shape[0]
+    fixed = torch.as_tensor(fixed_slot, dtype=torch.int32).to(dev).expand(B).contiguous()
+    if bool(((fixed < 0) | (fixed >= K)).any()):
+        raise ValueError(f"fixed_slot outside [0, {K})")
+    pose, _ = h.fb_frame_state(dm, states, frames)
+    fixed_pose = pose[torch.arange(B, device=dev), fixed.long()].contiguous()
+    return dict(trig_state=torch.zeros((B, K), dtype=torch.int32, device=dev),
+                trig_timers=torch.zeros((B, K, 2), dtype=torch.float64, device=dev), fixed_frame=fixed,
+                fixed_pose=fixed_pose)
+
+
 def nominal_com_offset(model):
     """The centre of mass relative to the base origin at the nominal posture (all joints 0, base
     orientation identity)."""

@@ -984,6 +984,77 @@ blf_status blf_fbd_euler_integrate(blf_handle* handle, const blf_fb_model* model
 
 }  // extern "C"
 
+// Section 13.  The checks both calls make alike: the sizes every sibling of section 10 checks, then the
+// slot count, then the trigger parameters (host memory: read here, no staged copy).
+static blf_status check_triggers(const char* fn, const blf_handle* handle, int32_t K, const double* params,
+                                 int32_t shared, int32_t steps, int64_t batch)
+{
+    BLF_REQUIRE(handle != nullptr, "%s: null handle", fn);
+    BLF_REQUIRE(steps >= 1, "%s: steps=%d, must be >= 1", fn, steps);
+    BLF_REQUIRE(batch >= 0, "%s: negative batch", fn);
+    BLF_REQUIRE(params != nullptr, "%s: null params", fn);
+    if (K < 1 || K > BLF_ODOM_MAX_CONTACTS)
+        return set_error(BLF_ERR_UNSUPPORTED, "%s: ncontacts=%d outside [1, %d]", fn, K, BLF_ODOM_MAX_CONTACTS);
+    for (int c = 0; c < (shared ? 1 : K); ++c) {
+        const double* p = params + 4 * c;
+        BLF_REQUIRE(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && std::isfinite(p[3]),
+                    "%s: params[%d] holds a threshold or delay that is not finite", fn, c);
+        BLF_REQUIRE(p[2] >= 0.0 && p[3] >= 0.0, "%s: params[%d] holds a negative delay", fn, c);
+        BLF_REQUIRE(p[0] >= p[1], "%s: params[%d]: on_threshold=%g below off_threshold=%g", fn, c, p[0], p[1]);
+    }
+    return BLF_OK;
+}
+
+extern "C" {
+
+blf_status blf_schmitt_trigger_advance(blf_handle* handle, int32_t ncontacts, const double* params,
+                                       int32_t shared_params, const double* time, const double* value,
+                                       int32_t steps, int32_t* state, double* timers, int32_t* state_out,
+                                       int64_t batch, void* stream)
+{
+    const char* fn = "blf_schmitt_trigger_advance";
+    const blf_status st = check_triggers(fn, handle, ncontacts, params, shared_params, steps, batch);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(time != nullptr, "%s: null time", fn);
+    BLF_REQUIRE(batch == 0 || value != nullptr, "%s: null value", fn);
+    BLF_REQUIRE(batch == 0 || state != nullptr, "%s: null state", fn);
+    BLF_REQUIRE(batch == 0 || timers != nullptr, "%s: null timers", fn);
+    return launch_schmitt_trigger(params, shared_params, ncontacts, time, value, steps, state, timers, state_out,
+                                  batch, (hipStream_t)stream);
+}
+
+blf_status blf_legged_odometry_advance(blf_handle* handle, const blf_fb_model* model, int32_t ncontacts,
+                                       const int32_t* frames, const double* params, int32_t shared_params,
+                                       const double* time, const double* joint_pos, const double* joint_vel,
+                                       const double* normal_force, int32_t steps, int32_t* trig_state,
+                                       double* trig_timers, int32_t* fixed_frame, double* fixed_pose,
+                                       double* base_pos, double* base_rot, double* base_vel,
+                                       int32_t* contact_out, int32_t* fixed_out, int32_t* status, int64_t batch,
+                                       int32_t reserved, void* stream)
+{
+    const char* fn = "blf_legged_odometry_advance";
+    BLF_REQUIRE(reserved == 0, "%s: reserved must be 0", fn);
+    BLF_REQUIRE(model != nullptr, "%s: null model", fn);
+    blf_status st = check_triggers(fn, handle, ncontacts, params, shared_params, steps, batch);
+    if (st == BLF_OK) st = check_ndof(fn, model, BLF_ERR_UNSUPPORTED);
+    if (st == BLF_OK) st = check_model_arrays(fn, model);
+    if (st != BLF_OK) return st;
+    BLF_REQUIRE(frames && model->frame_link && model->frame_pose && model->nframes > 0, "%s: null frame buffer", fn);
+    BLF_REQUIRE(time != nullptr, "%s: null time", fn);
+    BLF_REQUIRE(batch == 0 || joint_pos != nullptr, "%s: null joint_pos", fn);
+    BLF_REQUIRE(batch == 0 || normal_force != nullptr, "%s: null normal_force", fn);
+    BLF_REQUIRE(batch == 0 || (trig_state && trig_timers && fixed_frame && fixed_pose), "%s: null estimator state", fn);
+    BLF_REQUIRE(batch == 0 || base_pos || base_rot || base_vel || contact_out || fixed_out || status,
+                "%s: no output requested", fn);
+    st = check_lds(fn, odometry_lds_bytes(model->ndof, ncontacts), kInverse.lds);
+    if (st != BLF_OK) return st;
+    return launch_legged_odometry(model, ncontacts, frames, params, shared_params, time, joint_pos, joint_vel,
+                                  normal_force, steps, trig_state, trig_timers, fixed_frame, fixed_pose, base_pos,
+                                  base_rot, base_vel, contact_out, fixed_out, status, batch, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
 // The checks blf_fb_ik_solve and blf_fb_ik_integrate share.  The shared weight and gain arrays are
 // device memory: they are copied to the host on the call's stream and checked there before the
 // launch (section 12: a staged copy).

@@ -177,6 +177,17 @@ blf_status launch_fb_ik_track(const blf_fb_model* md, const blf_fb_state* st, co
                               uint32_t stance, double tau);
 size_t fb_ik_lds_bytes(int n, int K, bool limits = false);
 size_t fb_ik_track_lds_bytes(int n, int K);
+// Section 13.  params: HOST memory, already validated ([4] when shared, else [K][4])
+blf_status launch_schmitt_trigger(const double* params, int shared, int32_t K, const double* time,
+                                  const double* value, int32_t steps, int32_t* state, double* timers,
+                                  int32_t* state_out, int64_t batch, hipStream_t s);
+blf_status launch_legged_odometry(const blf_fb_model* md, int32_t K, const int32_t* frames, const double* params,
+                                  int shared, const double* time, const double* joint_pos, const double* joint_vel,
+                                  const double* normal_force, int32_t steps, int32_t* trig_state, double* trig_timers,
+                                  int32_t* fixed_frame, double* fixed_pose, double* base_pos, double* base_rot,
+                                  double* base_vel, int32_t* contact_out, int32_t* fixed_out, int32_t* status,
+                                  int64_t batch, hipStream_t s);
+size_t odometry_lds_bytes(int n, int K);
 blf_status launch_posture_reference(const blf_posture_law* law, const double* com, const double* vrp,
                                     int64_t vstride, int64_t batch, double* qref, hipStream_t s);
 blf_status launch_fbk_euler(int n, double rho, double* pos, double* rot, double* joints,

@@ -1112,6 +1112,90 @@ blf_status blf_fb_ik_track(blf_handle* handle, const blf_fb_model* model,
                            int32_t* fail_step /* [B] or NULL */, int32_t* iters /* [B] or NULL */,
                            uint64_t* active /* [B][2] or NULL */, void* stream);
 
+/* ---- 13. Contact detection and legged odometry (Contacts::SchmittTriggerDetector,
+ *          Estimators::LeggedOdometry), batched ---------------------------------------------------
+ * Both classes are absent from the reference snapshot (upstream added them later); this section
+ * defines them.  Everything is fp64 with no FMA contraction.
+ *
+ * The trigger.  A trigger has parameters (on_threshold, off_threshold, switch_on_after,
+ * switch_off_after), a state word (bit 0: the contact state, bit 1: an edge is pending; the other
+ * bits are dropped by the first finite sample) and two timers (edge_time, switch_time).  One sample
+ * (t, v), each test one subtraction and one comparison:
+ *   if v or t is not finite: the state and the timers are left as they are; otherwise
+ *   state off:  cross = v >= on_threshold,   after = switch_on_after
+ *   state on:   cross = v <= off_threshold,  after = switch_off_after
+ *   if cross and no edge is pending: pending, edge_time = t;  if not cross: not pending
+ *   if pending and (t - edge_time) >= after: the state flips, switch_time = t, not pending
+ * (so a delay of 0 switches on the sample that crosses, and a sample back inside the band clears a
+ * pending edge: chatter shorter than the delay never switches).
+ *
+ * blf_schmitt_trigger_advance: B x K independent triggers over T samples, samples STEP-MAJOR as in
+ * section 10.  params: HOST memory (read and validated during the call, never by the device), [4]
+ * when shared_params != 0, else [K][4].  time [T] (one clock for the batch), value [T][B][K]; state
+ * [B][K] int32 and timers [B][K][2] = (edge_time, switch_time) are updated in place; state_out
+ * [T][B][K] int32 or NULL: bit 0 after each sample.  Every other pointer is device memory.
+ * Errors: null handle, params or time, another null pointer with batch > 0 (state_out excepted),
+ * steps < 1, batch < 0, a threshold or delay
+ * that is not finite, a negative delay, on_threshold < off_threshold: BLF_ERR_INVALID_ARGUMENT;
+ * ncontacts outside [1, BLF_ODOM_MAX_CONTACTS]: BLF_ERR_UNSUPPORTED (checked before the parameter
+ * values); batch == 0: BLF_OK.                                                                    */
+#define BLF_ODOM_MAX_CONTACTS 8
+blf_status blf_schmitt_trigger_advance(blf_handle* handle, int32_t ncontacts, const double* params,
+                                       int32_t shared_params, const double* time, const double* value,
+                                       int32_t steps, int32_t* state, double* timers, int32_t* state_out,
+                                       int64_t batch, void* stream);
+
+/* blf_legged_odometry_advance: T steps of B estimators of the base pose and twist from the joint
+ * kinematics and a frame held fixed in the world, in ONE launch on `stream` (no staged copy, no
+ * host synchronisation: the call can be captured into a graph).
+ * fb_model: the robot (gravity, masses and inertias are not read; the arrays must still be there).
+ * frames [K]: the model's frame index of contact slot c.  params / shared_params / time: as above.  joint_pos
+ * [T][B][n], joint_vel [T][B][n] or NULL (zero), normal_force [T][B][K].
+ * Estimator state, in place: trig_state [B][K], trig_timers [B][K][2] (the K triggers), fixed_frame
+ * [B] int32 (a SLOT in [0, K)), fixed_pose [B][12] = (p, R row-major): the world transform at which
+ * that slot's frame is held.  To start from a known base pose, fixed_pose is blf_fb_frame_state's
+ * `pose` of that frame at the known state, the trigger state and timers zero (or bit 0 set for the
+ * feet on the ground).
+ * Outputs, step-major, each may be NULL but not all: base_pos [T][B][3], base_rot [T][B][9],
+ * base_vel [T][B][6] (mixed: blf_fb_state.base_vel's layout), contact_out [T][B][K] int32,
+ * fixed_out [T][B] int32 (the fixed slot after the step), status [B] int32.
+ * One step t of robot b:
+ *   1. the K triggers take (time[t], normal_force[t][b][c]) exactly as above: contact_out is
+ *      bit-identical to blf_schmitt_trigger_advance's state_out on the same samples
+ *   2. the forward kinematics of section 8 at joint_pos[t], joint_vel[t] with the base at the
+ *      identity and at rest: (p_c, R_c) the pose and (v_c, w_c) the mixed velocity of slot c's frame
+ *      relative to the base, in base coordinates
+ *   3. with f = fixed_frame and (P, Q) = fixed_pose:   R_B = Q R_f^T,   p_B = P - R_B p_f
+ *   4. the switch: f stays while slot f's state is on; otherwise f' = the slot whose state is on
+ *      with the greatest switch_time (the lowest slot among equals); if no slot is on, f stays (the
+ *      estimate dead-reckons on the last foot; an all-zero contact_out row reports it).  On a change
+ *      fixed_pose <- (p_B + R_B p_f', R_B R_f'), fixed_frame <- f'; the step's base pose is not
+ *      changed by the switch
+ *   5. the base twist that holds the (new) fixed frame at rest, in closed form:
+ *      w_B = -R_B w_f,   v_B = -R_B v_f - w_B x (R_B p_f)
+ * Rotations are composed and never re-orthonormalised (as ForwardEuler leaves base_rot): over a long
+ * walk fixed_pose's rotation drifts from SO(3) at rounding level per switch.
+ * A robot with a non-finite joint_pos, joint_vel or fixed_pose at some step, with fixed_frame
+ * outside [0, K), or whose kinematics are not finite (an unknown joint_type: NaN as in section 8)
+ * gets status BLF_IK_BAD_INPUT, NaN in base_pos / base_rot / base_vel from that step on and in
+ * fixed_pose, fixed_out = -1 from that step on, and keeps its fixed_frame; its triggers run on
+ * (contact_out, trig_state, trig_timers depend on the forces and times only).  A frames[c] outside
+ * [0, fb_model->nframes) gives every robot that treatment (never a read past the model).  No other
+ * robot is touched.  status is BLF_IK_OK otherwise.
+ * Errors: null handle, model, model array, frames, params or time, another required pointer null or
+ * no output requested with batch > 0, reserved != 0, steps < 1, batch < 0, a bad trigger parameter
+ * (above): BLF_ERR_INVALID_ARGUMENT; ndof outside
+ * [1, BLF_FBD_MAX_DOFS] or ncontacts outside [1, BLF_ODOM_MAX_CONTACTS]: BLF_ERR_UNSUPPORTED;
+ * batch == 0: BLF_OK.                                                                             */
+blf_status blf_legged_odometry_advance(blf_handle* handle, const blf_fb_model* fb_model, int32_t ncontacts,
+                                       const int32_t* frames, const double* params, int32_t shared_params,
+                                       const double* time, const double* joint_pos, const double* joint_vel,
+                                       const double* normal_force, int32_t steps, int32_t* trig_state,
+                                       double* trig_timers, int32_t* fixed_frame, double* fixed_pose,
+                                       double* base_pos, double* base_rot, double* base_vel,
+                                       int32_t* contact_out, int32_t* fixed_out, int32_t* status, int64_t batch,
+                                       int32_t reserved, void* stream);
+
 /* Algorithmic flop count of one IPM iteration of one problem (what the fp64 roofline field
  * of bench.py is computed from); `active_facets` = sum_k nfacets[k]. */
 double blf_dcm_mpc_flops_per_iter(int32_t horizon, int64_t active_facets);
