@@ -17,7 +17,7 @@
 // LIMITS kernels (section 12c, fb_ik_limits_kernel): an active-set iteration around steps 2b-5 on the
 // joints held at a bound of their velocity box, which step 3b eliminates from the system in place.
 // TRACK kernel (section 12d, fb_ik_track_kernel): the LIMITS loop with the set points and each robot's
-// own hard rows of step t (ik_solve_track: the union of a wavefront's two masks, null rows).
+// own hard rows of step t (ik_solve's TRACK: the union of a wavefront's two masks, null rows).
 // Built without the iterative-ILP scheduler of fb_dynamics.hip: LLVM's register allocator crashes
 // on the 54-row instantiation with it (the reason this kernel has a file of its own).
 #include "fb_common.h"
@@ -85,6 +85,25 @@ struct IkSmem {
     __device__ __forceinline__ double* pb(int n) const { return S.base + o_lim + 3 * n; }
 };
 
+// fb_ik_track_kernel's layout (section 12d): the LIMITS one, and room for the packed factor of S where
+// the link records cannot hold it (a wavefront's two robots factor the union of their hard rows, up to
+// min(27, 6 K + 3) of them whatever n is).  A struct of its own, which ik_solve takes as a template
+// argument: a field in IkSmem would be carried by every IK kernel.
+struct IkTrackSmem : IkSmem {
+    int o_cf;
+    __host__ __device__ IkTrackSmem(double* b, int n, int K, int nvmax) : IkSmem(b, n, K, nvmax, true)
+    {
+        const int mu = 6 * K + 3 < kIkRows ? 6 * K + 3 : kIkRows;
+        const size_t cf = (size_t)mu * (mu + 1) / 2;
+        o_cf = S.o_link;
+        if (cf > (size_t)S.lrec * (n + 1)) {
+            o_cf = (int)total;
+            total += (cf + 1) & ~size_t(1);
+        }
+    }
+    __device__ __forceinline__ double* cf() const { return S.base + o_cf; }
+};
+
 // One solve for the robot whose state sits in S.st() (zero velocities | bp | bR | jp) and whose
 // set points sit in I.sp().  Leaves nu in S.rhs(); false if a pivot was not finite and positive.
 // HARD (section 12b): the rows of hd.slots hold exactly; hdep: a pivot of S failed its rule.
@@ -93,14 +112,24 @@ struct IkSmem {
 // joint j, this lane's robot) fixed at I.fx(): they are eliminated from the system in place, a fixed
 // lane's row of H becoming e_i and its g_i the bound, a free lane's fixed columns moving to g_i.  The
 // hard rows' multipliers are then left in I.col() by table row.
+// TRACK (section 12d, SM = IkTrackSmem): the hard rows differ between the two robots of a wavefront.
+// hd.slots is the union of their masks (wave-uniform, so the unrolled loops of 4b stay scalar
+// branches) and `hme` this robot's own.  A row of the union that this robot does not hold is a null
+// row: its y is 0, its row of S is e_i and its q is 0, so it passes the pivot rule with lambda = 0 and
+// adds exact zeros to every other row: the robot's own rows see the arithmetic they see alone.  The
+// union may count more than NV rows (each robot's own count is judged by the kernel), and S's packed
+// factor goes to I.cf().
 constexpr int kPrep = 1, kRows = 2, kSolve = 4;
-template <int NVMAX, int HW, bool PRI, bool HARD, bool LIMITS = false, int PH = kPrep | kRows | kSolve>
-__device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const IkTasks& tk, const Topo& T,
-                                         const IkHard& hd, bool& hdep, unsigned long long wm = 0ull)
+template <int NVMAX, int HW, bool PRI, bool HARD, bool LIMITS = false, int PH = kPrep | kRows | kSolve,
+          bool TRACK = false, class SM = IkSmem>
+__device__ __forceinline__ bool ik_solve(const Model& m, const SM& I, const IkTasks& tk, const Topo& T,
+                                         const IkHard& hd, bool& hdep, unsigned long long wm = 0ull,
+                                         unsigned hme = 0u)
 {
     static_assert(NVMAX <= HW, "a robot's rows must fit its lanes");
     static_assert(LIMITS || PH == (kPrep | kRows | kSolve), "only the LIMITS kernels run in phases");
     static_assert(HARD || !LIMITS, "the LIMITS kernels are built on the HARD ones (slots may be 0)");
+    static_assert(!TRACK || (HARD && LIMITS), "the TRACK kernel is built on the LIMITS ones");
     const Half<HW> H;
     const Smem& S = I.S;
     const int n = m.n, L = n + 1, NV = n + 6, MS = S.ms, K = tk.K;
@@ -313,7 +342,9 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
         //     rows intact in I.rows().  Hard row i (in row order) belongs to lane i from step (ii) on.
         const unsigned hm = hd.slots;   // wave-uniform
         const int mh = __builtin_popcount(hm);
-        bool hok = mh <= NV;   // more hard rows than unknowns: dependent (and the factor would not fit)
+        // more hard rows than unknowns: dependent (and the factor would not fit); TRACK: the union may
+        // hold more than NV, each robot's own count is judged by the kernel and the factor has I.cf()
+        bool hok = TRACK || mh <= NV;
         if constexpr (LIMITS) {
             if (lane < kIkRows) I.col()[lane] = 0.0;   // the multipliers by table row (H's factor is done with it)
             wave_sync();
@@ -345,7 +376,8 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
                 for (int g = 0; g < G; ++g) {
                     t[g] = rest != 0u ? __builtin_ctz(rest) : -1;
                     rest = rest != 0u ? rest & (rest - 1u) : 0u;
-                    v[g] = t[g] >= 0 && lane < NV && !fixed ? rows[t[g] * I.rs + cl] : 0.0;
+                    const bool mine = !TRACK || ((hme >> (t[g] & 31)) & 1u);
+                    v[g] = t[g] >= 0 && lane < NV && !fixed && mine ? rows[t[g] * I.rs + cl] : 0.0;
                 }
 #pragma unroll
                 for (int k = 0; k < NVMAX; ++k) {
@@ -390,13 +422,21 @@ __device__ __forceinline__ bool ik_solve(const Model& m, const IkSmem& I, const 
                 }
                 q = q - (LIMITS ? I.wt()[kIkRows + own] - moved : I.wt()[kIkRows + own]);
             }
+            if constexpr (TRACK) {
+                const bool null = !((hme >> own) & 1u);
+                q = null ? 0.0 : q;
+#pragma unroll
+                for (int t = 0; t < kIkRows; ++t) sr[t] = null ? (own == t ? 1.0 : 0.0) : sr[t];
+            }
             double d0 = 0.0;   // S_ii before elimination
 #pragma unroll
             for (int t = 0; t < kIkRows; ++t) d0 = own == t ? sr[t] : d0;
             // (iii) S = C C^T, lane per row: pivot p (table row t) is lane p's sr[t]; column p of C
             //       goes to LDS packed (entries p..m_h-1), over the link records, which are dead
-            //       until the next kinematics: m_h (m_h + 1) / 2 <= 27 (n + 1) since m_h <= min(27, NV)
+            //       until the next kinematics: m_h (m_h + 1) / 2 <= 27 (n + 1) since m_h <= min(27, NV).
+            //       TRACK: to I.cf(), which is the link records where the union's factor fits them
             double* ct = S.link();
+            if constexpr (TRACK) ct = I.cf();
             double cdi = 0.0;   // 1 / C_ii of the lane's own row
             {
                 int p = 0;
@@ -742,433 +782,6 @@ __global__ __launch_bounds__(64) void fb_ik_limits_kernel(Model m, blf_fb_state 
     if (active_out && lane < 2) active_out[2 * q + lane] = stat != BLF_IK_OK ? 0ull : lane == 0 ? wl : wu;
 }
 
-// fb_ik_track_kernel's layout (section 12d): the LIMITS one, and room for the packed factor of S where
-// the link records cannot hold it (a wavefront's two robots factor the union of their hard rows, up to
-// min(27, 6 K + 3) of them whatever n is).
-struct IkTrackSmem : IkSmem {
-    int o_cf;
-    __host__ __device__ IkTrackSmem(double* b, int n, int K, int nvmax) : IkSmem(b, n, K, nvmax, true)
-    {
-        const int mu = 6 * K + 3 < kIkRows ? 6 * K + 3 : kIkRows;
-        const size_t cf = (size_t)mu * (mu + 1) / 2;
-        o_cf = S.o_link;
-        if (cf > (size_t)S.lrec * (n + 1)) {
-            o_cf = (int)total;
-            total += (cf + 1) & ~size_t(1);
-        }
-    }
-    __device__ __forceinline__ double* cf() const { return S.base + o_cf; }
-};
-
-// ik_solve<NVMAX, HW, PRI, true, true, PH> for fb_ik_track_kernel, as text of its own: sharing ik_solve
-// through one more template parameter moved the register allocation of the HARD and LIMITS kernels
-// (scratch where they had none).  What differs from ik_solve: the hard rows differ between the two
-// robots of a wavefront.  hd.slots is the union of their masks (wave-uniform, so the unrolled loops
-// of 4b stay scalar branches) and `hme` this robot's own.  A row of the union that this robot does not
-// hold is a null row: its y is 0, its row of S is e_i and its q is 0, so it passes the pivot rule with
-// lambda = 0 and adds exact zeros to every other row: the robot's own rows see the arithmetic they see
-// alone.  The union may count more than NV rows (each robot's own count is judged by the kernel), and
-// S's packed factor goes to I.cf().
-template <int NVMAX, int HW, bool PRI, int PH>
-__device__ __forceinline__ bool ik_solve_track(const Model& m, const IkTrackSmem& I, const IkTasks& tk,
-                                               const Topo& T, const IkHard& hd, bool& hdep,
-                                               unsigned long long wm = 0ull, unsigned hme = 0u)
-{
-    static_assert(NVMAX <= HW, "a robot's rows must fit its lanes");
-    constexpr bool HARD = true, LIMITS = true, TRACK = true;
-    const Half<HW> H;
-    const Smem& S = I.S;
-    const int n = m.n, L = n + 1, NV = n + 6, MS = S.ms, K = tk.K;
-    int lane = H.hl;
-    asm volatile("" : "+v"(lane));   // see fbd_eval
-    double* loc = S.st();
-    const double* jp = loc + 18 + n;
-    const double* sp = I.sp();
-    const bool com = tk.cw != nullptr;
-    const int M = 6 * K + (com ? 3 : 0);
-    // 1. kinematics
-    if constexpr ((PH & kPrep) != 0) fbd_kinematics<HW, PRI>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, jp, T);
-    // (LIMITS: the base position, which 2b reads again after S's factor has gone over the link records)
-    if (LIMITS && (PH & kPrep) && lane < 3) I.pb(n)[lane] = S.link()[kP + lane];
-    // 2a. lane per link: m_l and m_l c_l; lane per task: the frame's origin, the target twist, the link
-    if ((PH & kPrep) && com && lane < L) {
-        const double* k = S.link() + S.lrec * lane;
-        const double* R = k + kR;
-        const double* cl = m.com + 3 * lane;
-        const double ms = m.mass[lane];
-        double* o = I.mc() + kIkMc * lane;
-        o[0] = ms;
-        for (int a = 0; a < 3; ++a)
-            o[1 + a] = ms * (k[kP + a] + ((R[3 * a] * cl[0] + R[3 * a + 1] * cl[1]) + R[3 * a + 2] * cl[2]));
-    }
-    if ((PH & kPrep) && lane < K) {
-        int f = tk.frame[lane];
-        f = (f >= 0 && f < m.F) ? f : 0;   // out of range: the robot is BLF_IK_BAD_INPUT already
-        const int l = m.flink[f];
-        double pose[12], tw[6], u[3], th;
-        frame_state(S.link() + S.lrec * l, m.fpose + 12 * f, pose, tw);
-        const double* des = sp + 12 * lane;
-        const double* ff = sp + 12 * K + 6 * lane;
-        so3_log_rel(des + 3, pose + 3, u, th);
-        const double kpl = tk.kp[2 * lane], kpa = tk.kp[2 * lane + 1];
-        double* o = I.ts() + kIkTs * lane;
-        for (int a = 0; a < 3; ++a) {
-            o[a] = pose[a];
-            o[3 + a] = ff[a] + kpl * (des[a] - pose[a]);
-            o[6 + a] = ff[3 + a] + kpa * (th * u[a]);
-        }
-        o[9] = (double)l;
-    }
-    wave_sync();
-    // 2b. lane per column c: its motion (angular axis w about the point o, linear part u) and from
-    //     it column c of every task row: u + w x (x - o) | w for a point x the column moves
-    if constexpr ((PH & kRows) != 0) {
-        const double* pB = LIMITS ? I.pb(n) : S.link() + kP;
-        const int j = lane >= 6 && lane < NV ? lane - 6 : 0;
-        const bool jc = lane >= 6 && lane < NV;
-        const bool pri = PRI && jc && m.jtype[j] == BLF_JOINT_PRISMATIC;
-        double w[3], u[3], o[3];
-        for (int a = 0; a < 3; ++a) {
-            const double z = S.jz()[3 * j + a];
-            w[a] = jc ? (pri ? 0.0 : z) : (lane == 3 + a ? 1.0 : 0.0);
-            u[a] = jc ? (pri ? z : 0.0) : (lane == a ? 1.0 : 0.0);
-            o[a] = jc ? S.jo()[3 * j + a] : pB[a];
-        }
-        double* rows = I.rows();
-        for (int k = 0; k < K; ++k) {
-            const double* t = I.ts() + kIkTs * k;
-            const unsigned long long an = S.anc()[(int)t[9]];
-            const bool moves = lane < 6 || (jc && ((an >> j) & 1ull));
-            double d[3], cr[3];
-            for (int a = 0; a < 3; ++a) d[a] = t[a] - o[a];
-            cross3(w, d, cr);
-            if (lane < NVMAX)
-                for (int a = 0; a < 3; ++a) {
-                    rows[(6 * k + a) * I.rs + lane] = moves ? u[a] + cr[a] : 0.0;
-                    rows[(6 * k + 3 + a) * I.rs + lane] = moves ? w[a] : 0.0;
-                }
-        }
-        if (com) {
-            double tm = 0.0, th[3] = {0.0, 0.0, 0.0}, sm = 0.0, sh[3] = {0.0, 0.0, 0.0};
-            for (int l = 0; l < L; ++l) {
-                const double* q = I.mc() + kIkMc * l;
-                const bool in = jc && ((S.anc()[l] >> j) & 1ull);
-                tm = tm + q[0];
-                sm = in ? sm + q[0] : sm;
-                for (int a = 0; a < 3; ++a) {
-                    th[a] = th[a] + q[1 + a];
-                    sh[a] = in ? sh[a] + q[1 + a] : sh[a];
-                }
-            }
-            double c[3], d[3], cr[3];
-            for (int a = 0; a < 3; ++a) {
-                c[a] = th[a] / tm;
-                d[a] = jc ? (sh[a] - sm * o[a]) / tm : c[a] - o[a];
-            }
-            cross3(w, d, cr);
-            const double us = jc ? sm / tm : 1.0;
-            if (lane < NVMAX)
-                for (int a = 0; a < 3; ++a) rows[(6 * K + a) * I.rs + lane] = lane < NV ? u[a] * us + cr[a] : 0.0;
-            if (lane < 3) {
-                const double* cd = sp + 18 * K;
-                // (selects, not a lane-indexed array: that would live in scratch)
-                const double ca = lane == 0 ? c[0] : lane == 1 ? c[1] : c[2];
-                I.wt()[kIkRows + 6 * K + lane] = cd[3 + lane] + tk.ckp * (cd[lane] - ca);
-                I.wt()[6 * K + lane] = tk.cw[lane];
-            }
-        }
-        if (lane < 6 * K) {
-            I.wt()[lane] = tk.w[lane];
-            I.wt()[kIkRows + lane] = I.ts()[kIkTs * (lane / 6) + 3 + lane % 6];
-        }
-    }
-    wave_sync();
-    if constexpr ((PH & kSolve) == 0) return true;
-    // 3. row `lane` of H (its lower part; the entries above the diagonal are never read) and g
-    double r[NVMAX], y = 0.0;
-#pragma unroll
-    for (int j = 0; j < NVMAX; ++j) r[j] = 0.0;
-    for (int t = 0; t < M; ++t) {
-        const double wr = I.wt()[t];
-        if (wr == 0.0) continue;   // a dropped row (the weights are shared: wave-uniform)
-        const double* a = I.rows() + t * I.rs;
-        const double ai = lane < NV ? a[lane < NVMAX ? lane : 0] * wr : 0.0;
-        y = fma(ai, I.wt()[kIkRows + t], y);
-#pragma unroll
-        for (int j = 0; j < NVMAX; ++j) r[j] = fma(ai, a[j], r[j]);
-    }
-    {
-        const int j = lane >= 6 && lane < NV ? lane - 6 : 0;
-        const double jw = tk.jw[j];
-        const double dg = lane < 6 ? tk.damp : lane < NV ? jw : 0.0;
-        const double sd = sp[18 * K + 6 + n + j] + tk.jkp[j] * (sp[18 * K + 6 + j] - jp[j]);
-        y = lane >= 6 && lane < NV ? y + jw * sd : y;
-#pragma unroll
-        for (int k = 0; k < NVMAX; ++k) r[k] = lane == k ? r[k] + dg : r[k];
-    }
-    // 3b. LIMITS: the fixed joints leave the system (selects over the unrolled columns: the sets of
-    //     a wavefront's two robots differ)
-    bool fixed = false;   // this lane's column is one of them
-    if constexpr (LIMITS) {
-        const double* fx = I.fx(n);
-        fixed = lane >= 6 && lane < NV && ((wm >> (lane - 6)) & 1ull);
-#pragma unroll
-        for (int j = 6; j < NVMAX; ++j) {
-            const bool fj = (wm >> (j - 6)) & 1ull;   // (no bit at or above n is ever set)
-            const double b = fx[j < NV ? j - 6 : 0];
-            y = fj ? y - r[j] * b : y;
-            r[j] = fj ? 0.0 : r[j];
-        }
-        y = fixed ? fx[fixed ? lane - 6 : 0] : y;
-#pragma unroll
-        for (int k = 0; k < NVMAX; ++k) r[k] = fixed ? (lane == k ? 1.0 : 0.0) : r[k];
-    }
-    // 4. Cholesky H = L L^T and the substitutions: fbd_eval's steps 8 and 9 (see there), with the
-    //    pivot also required to be finite
-    bool ok = true;
-    constexpr int CB = 2;
-    static_assert(NVMAX % CB == 0, "block size divides the register row");
-#pragma unroll
-    for (int k = 0; k < NVMAX; k += CB) {
-        if (k < NV) {
-            double Lb[CB][CB], il[CB];
-#pragma unroll
-            for (int i = 0; i < CB; ++i) {
-                const bool in = k + i < NV;
-#pragma unroll
-                for (int j = 0; j < i; ++j) {
-                    double t = in ? H.bcast_k(r[k + j], k + i) : 0.0;
-#pragma unroll
-                    for (int c = 0; c < j; ++c) t = t - Lb[i][c] * Lb[j][c];
-                    Lb[i][j] = t * il[j];
-                }
-                double d = in ? H.bcast_k(r[k + i], k + i) : 1.0;
-#pragma unroll
-                for (int c = 0; c < i; ++c) d = d - Lb[i][c] * Lb[i][c];
-                ok = ok && (d > 0.0) && (d <= 1.7976931348623157e308);
-                double q = __builtin_amdgcn_rsq(d);
-                il[i] = q * (1.5 - (0.5 * d) * (q * q));
-                Lb[i][i] = d * il[i];
-            }
-            double li[CB];
-#pragma unroll
-            for (int i = 0; i < CB; ++i) {
-                double t = r[k + i];
-#pragma unroll
-                for (int c = 0; c < i; ++c) t = t - li[c] * Lb[i][c];
-                li[i] = t * il[i];
-            }
-            double* col = I.col() + ((k / CB) & 1) * CB * NV;
-#pragma unroll
-            for (int i = 0; i < CB; ++i) {
-                r[k + i] = lane >= k ? li[i] : r[k + i];
-                if (lane < NV && k + i < NV) col[i * NV + lane] = r[k + i];
-            }
-            wave_sync();
-#pragma unroll
-            for (int j = k + CB; j < NVMAX; ++j) {
-                const int jj = j < NV ? j : NV - 1;
-                double t = r[j];
-#pragma unroll
-                for (int i = CB - 1; i >= 0; --i) t = fma(-r[k + i], col[i * NV + jj], t);
-                r[j] = t;
-            }
-        }
-    }
-    const double idg = lane < NV ? 1.0 / bcast_own_diag<NVMAX>(r, lane) : 0.0;
-#pragma unroll
-    for (int k = 0; k < NVMAX; ++k) {
-        y = lane == k ? y * idg : y;
-        const double xk = H.bcast_k(y, k);
-        const double f = lane > k ? r[k] : 0.0;
-        y = y - f * xk;
-    }
-    if constexpr (HARD) {
-        // 4b. the hard rows (section 12b).  L's rows are still in r[], z = L^-1 g in y, and the task
-        //     rows intact in I.rows().  Hard row i (in row order) belongs to lane i from step (ii) on.
-        const unsigned hm = hd.slots;   // wave-uniform
-        const int mh = __builtin_popcount(hm);
-        // more hard rows than unknowns: dependent (and the factor would not fit); TRACK: the union may
-        // hold more than NV, each robot's own count is judged by the kernel and the factor has I.cf()
-        bool hok = TRACK || mh <= NV;
-        if constexpr (LIMITS) {
-            if (lane < kIkRows) I.col()[lane] = 0.0;   // the multipliers by table row (H's factor is done with it)
-            wave_sync();
-        }
-        if (hok && (!LIMITS || mh > 0)) {
-            double* rows = I.rows();
-            const int cl = lane < NVMAX ? lane : 0;
-            // LIMITS: the fixed columns leave the hard rows too, a_t . (fixed values) leaves their targets
-            double moved = 0.0;
-            if constexpr (LIMITS) {
-                int ow = 0, p = 0;
-#pragma unroll
-                for (int t = 0; t < kIkRows; ++t)
-                    if ((hm >> t) & 1u) {
-                        ow = lane == p ? t : ow;
-                        ++p;
-                    }
-                const double* ao = rows + ow * I.rs + 6;
-                const double* fx = I.fx(n);
-                for (int j = 0; j < n; ++j) moved = fma(ao[j], fx[j], moved);
-            }
-            // (i) Y = L^-1 A_h^T: the forward substitution above on each hard row, three right-hand
-            //     sides at a time (independent chains), y_t written back over row t
-            constexpr int G = 3;
-            for (unsigned rest = hm; rest != 0u;) {
-                int t[G];
-                double v[G];
-#pragma unroll
-                for (int g = 0; g < G; ++g) {
-                    t[g] = rest != 0u ? __builtin_ctz(rest) : -1;
-                    rest = rest != 0u ? rest & (rest - 1u) : 0u;
-                    const bool mine = !TRACK || ((hme >> (t[g] & 31)) & 1u);
-                    v[g] = t[g] >= 0 && lane < NV && !fixed && mine ? rows[t[g] * I.rs + cl] : 0.0;
-                }
-#pragma unroll
-                for (int k = 0; k < NVMAX; ++k) {
-                    const double f = lane > k ? r[k] : 0.0;
-#pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        v[g] = lane == k ? v[g] * idg : v[g];
-                        const double xk = H.bcast_k(v[g], k);
-                        v[g] = v[g] - f * xk;
-                    }
-                }
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                    if (t[g] >= 0 && lane < NVMAX) rows[t[g] * I.rs + lane] = v[g];
-            }
-            if (lane < NV) S.rhs()[lane] = y;   // z, for the lanes of (ii)
-            wave_sync();
-            // (ii) lane i < m_h: row i of S = Y^T Y, indexed by table row (entries of soft rows stay
-            //      0 and are never read), and q_i = y_i . z - b_i
-            int own = 0;
-            {
-                int p = 0;
-#pragma unroll
-                for (int t = 0; t < kIkRows; ++t)
-                    if ((hm >> t) & 1u) {
-                        own = lane == p ? t : own;
-                        ++p;
-                    }
-            }
-            double sr[kIkRows], q = 0.0;
-#pragma unroll
-            for (int t = 0; t < kIkRows; ++t) sr[t] = 0.0;
-            {
-                const double* yo = rows + own * I.rs;
-                const double* z = S.rhs();
-                for (int c = 0; c < NV; ++c) {
-                    const double yi = yo[c];
-                    q = fma(yi, z[c], q);
-#pragma unroll
-                    for (int t = 0; t < kIkRows; ++t)
-                        if ((hm >> t) & 1u) sr[t] = fma(yi, rows[t * I.rs + c], sr[t]);
-                }
-                q = q - (LIMITS ? I.wt()[kIkRows + own] - moved : I.wt()[kIkRows + own]);
-            }
-            if constexpr (TRACK) {
-                const bool null = !((hme >> own) & 1u);
-                q = null ? 0.0 : q;
-#pragma unroll
-                for (int t = 0; t < kIkRows; ++t) sr[t] = null ? (own == t ? 1.0 : 0.0) : sr[t];
-            }
-            double d0 = 0.0;   // S_ii before elimination
-#pragma unroll
-            for (int t = 0; t < kIkRows; ++t) d0 = own == t ? sr[t] : d0;
-            // (iii) S = C C^T, lane per row: pivot p (table row t) is lane p's sr[t]; column p of C
-            //       goes to LDS packed (entries p..m_h-1), to I.cf(): over the link records, which are
-            //       dead until the next kinematics, where the union's m_h (m_h + 1) / 2 fit there
-            double* ct = TRACK ? I.cf() : S.link();
-            double cdi = 0.0;   // 1 / C_ii of the lane's own row
-            {
-                int p = 0;
-#pragma unroll
-                for (int t = 0; t < kIkRows; ++t)
-                    if ((hm >> t) & 1u) {
-                        const double d = H.bcast_k(sr[t], p);
-                        const double dd = H.bcast_k(d0, p);
-                        hok = hok && (d > hd.tau * dd) && (d <= 1.7976931348623157e308);
-                        const double qq = __builtin_amdgcn_rsq(d);
-                        const double il = qq * (1.5 - (0.5 * d) * (qq * qq));
-                        const double l = sr[t] * il;
-                        sr[t] = l;
-                        cdi = lane == p ? il : cdi;
-                        double* col = ct + (p * mh - (p * (p - 1)) / 2);
-                        if (lane >= p && lane < mh) col[lane - p] = l;
-                        wave_sync();
-                        int pu = 1;
-#pragma unroll
-                        for (int u = t + 1; u < kIkRows; ++u)
-                            if ((hm >> u) & 1u) {
-                                sr[u] = fma(-l, col[pu], sr[u]);
-                                ++pu;
-                            }
-                        ++p;
-                    }
-            }
-            // (iv) lambda = C^-T C^-1 q
-            {
-                int p = 0;
-#pragma unroll
-                for (int t = 0; t < kIkRows; ++t)
-                    if ((hm >> t) & 1u) {
-                        q = lane == p ? q * cdi : q;
-                        const double xk = H.bcast_k(q, p);
-                        const double f = lane > p ? sr[t] : 0.0;
-                        q = q - f * xk;
-                        ++p;
-                    }
-            }
-            {
-                const int li = lane < mh ? lane : 0;
-                const double* mycol = ct + (li * mh - (li * (li - 1)) / 2) - li;   // C[p][lane] at [p]
-                for (int p = mh - 1; p >= 0; --p) {
-                    q = lane == p ? q * cdi : q;
-                    const double xk = H.bcast_k(q, p);
-                    const double f = lane < p ? mycol[p] : 0.0;
-                    q = q - f * xk;
-                }
-            }
-            if constexpr (LIMITS)
-                if (lane < mh) I.col()[own] = q;
-            // (v) z - Y lambda
-            {
-                int p = 0;
-#pragma unroll
-                for (int t = 0; t < kIkRows; ++t)
-                    if ((hm >> t) & 1u) {
-                        const double lam = H.bcast_k(q, p);
-                        const double yt = lane < NV ? rows[t * I.rs + cl] : 0.0;
-                        y = y - yt * lam;
-                        ++p;
-                    }
-            }
-            wave_sync();   // the rows are read; L goes over them next
-        }
-        hdep = !hok;
-    }
-    double* Lr = I.rows();
-    if (lane < NV)
-#pragma unroll
-        for (int j = 0; j < NVMAX; ++j)
-            if (j < NV && j <= lane) Lr[MS * lane + j] = r[j];
-    wave_sync();
-    double lki = (lane < NV - 1) ? Lr[MS * (NV - 1) + lane] : 0.0;
-    for (int k = NV - 1; k >= 0; --k) {
-        const double lnext = (k > 0 && lane < k - 1) ? Lr[MS * (k - 1) + lane] : 0.0;
-        if (lane == k) y = y * idg;
-        const double xk = H.bcast_k(y, k);
-        if (lane < k) y = y - lki * xk;
-        lki = lnext;
-    }
-    // 5. nu
-    if (lane < NV) S.rhs()[lane] = y;
-    wave_sync();
-    return H.ballot(!ok) == 0ull;
-}
-
 // Section 12d as the kernel takes it: the schedule's arrays, the masks in the kernel's row bits (the
 // CoM bits moved down to 6 K, as IkHard::slots) and the trajectories.
 struct IkTrack {
@@ -1183,7 +796,7 @@ struct IkTrack {
 // blf_fb_ik_track: fb_ik_limits_kernel's step with the set points and the hard mask of step t, the
 // state in LDS over the T steps.  Per step only the 18 K + 6 set points of that step are staged again
 // (the joint task's are held), and each robot's mask is rebuilt from its contact flags; the solve
-// takes the union of the wavefront's two masks (ik_solve_track).  A robot whose own mask counts more
+// takes the union of the wavefront's two masks (ik_solve's TRACK).  A robot whose own mask counts more
 // than 6 + n rows solves with an empty one (all null rows, which cannot fail) and is marked
 // dependent here.  lp.lower == nullptr: no box (every iteration ends after its first solve).
 template <int NVMAX, int HW, bool PRI>
@@ -1284,7 +897,7 @@ __global__ __launch_bounds__(64) void fb_ik_track_kernel(Model m, blf_fb_state s
             I.fx(n)[lane] = 0.0;
         }
         bool hdep = false;
-        ik_solve_track<NVMAX, HW, PRI, kPrep | kRows>(m, I, tk, T, hd, hdep);
+        ik_solve<NVMAX, HW, PRI, true, true, kPrep | kRows, true>(m, I, tk, T, hd, hdep);
         // the active-set iteration of fb_ik_limits_kernel (see there)
         bool done = stat != BLF_IK_OK, block = true;
         int best = 0x7fffffff, stall = 0, nit = 0;
@@ -1293,7 +906,7 @@ __global__ __launch_bounds__(64) void fb_ik_track_kernel(Model m, blf_fb_state s
         wu = 0ull;
         while (__ballot(!done)) {
             const unsigned long long wm = wl | wu;
-            const bool ok = ik_solve_track<NVMAX, HW, PRI, kSolve>(m, I, tk, T, hd, hdep, wm, mine);
+            const bool ok = ik_solve<NVMAX, HW, PRI, true, true, kSolve, true>(m, I, tk, T, hd, hdep, wm, mine);
             hdep = hdep || over;
             nit = done ? nit : nit + 1;
             const int s1 = !ok ? BLF_IK_NOT_POSITIVE : hdep && wm == 0ull ? BLF_IK_HARD_DEPENDENT : BLF_IK_OK;
@@ -1312,7 +925,7 @@ __global__ __launch_bounds__(64) void fb_ik_track_kernel(Model m, blf_fb_state s
             const unsigned long long vl = H.ballot(go && jc && !held && v < lo) >> 6;
             const unsigned long long vu = H.ballot(go && jc && !held && v > up) >> 6;
             unsigned long long rl = 0ull, ru = 0ull;
-            if (__ballot(!done)) ik_solve_track<NVMAX, HW, PRI, kRows>(m, I, tk, T, hd, hdep);
+            if (__ballot(!done)) ik_solve<NVMAX, HW, PRI, true, true, kRows, true>(m, I, tk, T, hd, hdep);
             if (__ballot(go && wm != 0ull)) {
                 const double rho = ik_rho<HW>(m, I, tk);
                 rl = H.ballot(go && jc && ((wl >> j) & 1ull) && rho > 0.0) >> 6;
