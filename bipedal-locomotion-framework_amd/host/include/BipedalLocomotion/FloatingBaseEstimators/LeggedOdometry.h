@@ -23,8 +23,8 @@
 #include <vector>
 
 #include <BipedalLocomotion/ParametersHandler/IParametersHandler.h>
-#include <BipedalLocomotion/System/FloatingBaseSystemDynamics.h>   // blf::RobotModel
 #include <blf/device.h>
+#include <blf/robot_model.h>
 #include <blf/spatial.h>
 
 namespace BipedalLocomotion
@@ -82,7 +82,7 @@ private:
     State m_state{State::NotInitialized};
     std::string m_initialFixedFrame;
     std::vector<std::string> m_names;
-    blf::RobotModel m_model;
+    blf::DeviceRobotModel m_model;
     std::vector<double> m_q, m_dq;
     bool m_hasKinematics{false};
     std::vector<int32_t> m_trigState;   // [K]
@@ -92,8 +92,8 @@ private:
     blf::Transform m_fixedPose;
     LeggedOdometryOutput m_output;
 
-    blf::DeviceBuffer<int32_t> m_dParent, m_dFrameLink, m_dJointType, m_dInts;
-    blf::DeviceBuffer<double> m_dOrigin, m_dRot, m_dAxis, m_dMass, m_dCom, m_dInertia, m_dFramePose, m_dData;
+    blf::DeviceBuffer<int32_t> m_dInts;
+    blf::DeviceBuffer<double> m_dData;
 
     int slot(const std::string& name) const;
 };

@@ -38,9 +38,9 @@
 #include <BipedalLocomotion/IK/JointTrackingTask.h>
 #include <BipedalLocomotion/IK/SE3Task.h>
 #include <BipedalLocomotion/System/Advanceable.h>
-#include <BipedalLocomotion/System/FloatingBaseSystemDynamics.h>   // blf::RobotModel
 #include <blf/dense.h>
 #include <blf/device.h>
+#include <blf/robot_model.h>
 #include <blf/spatial.h>
 
 namespace BipedalLocomotion
@@ -139,15 +139,14 @@ private:
     std::vector<double> m_limits;   // finalize(): pos_lower n | pos_upper n | klim n | vel_max n (or none)
     bool m_isFinalized{false}, m_hasModel{false}, m_hasState{false}, m_isValid{false};
     double m_baseDamping{0.0}, m_hardWeight{1.0};
-    blf::RobotModel m_model;
+    blf::DeviceRobotModel m_model;
     std::vector<std::string> m_frameNames;
     blf::Vector3 m_basePosition{};
     blf::Matrix3 m_baseRotation{};
     blf::VectorXd m_jointPositions;
     IntegrationBasedIKState m_state;
 
-    blf::DeviceBuffer<int32_t> m_dParent, m_dFrameLink, m_dJointType, m_dInt;
-    blf::DeviceBuffer<double> m_dOrigin, m_dRot, m_dAxis, m_dMass, m_dCom, m_dInertia, m_dFramePose;
+    blf::DeviceBuffer<int32_t> m_dInt;
     blf::DeviceBuffer<double> m_dData;
     blf_fb_model m_cModel{};
     blf_fb_state m_cState{};

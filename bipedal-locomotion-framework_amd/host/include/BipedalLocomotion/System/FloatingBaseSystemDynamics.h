@@ -29,48 +29,8 @@
 #include <BipedalLocomotion/System/DynamicalSystem.h>
 #include <blf/dense.h>
 #include <blf/device.h>
+#include <blf/robot_model.h>
 #include <blf/spatial.h>
-
-namespace blf
-{
-/** Kinematic tree of revolute, prismatic (jointType) and fixed (fixedJoint) joints on a floating
- *  base (see blf_fb_model in blf_c.h). */
-struct RobotModel
-{
-    int ndof{0};
-    std::vector<int32_t> parent;       /**< [n]        */
-    std::vector<double> jointOrigin;   /**< [n][3]     */
-    std::vector<double> jointRotation; /**< [n][9]     */
-    std::vector<double> jointAxis;     /**< [n][3]     */
-    std::vector<double> linkMass;      /**< [n+1]      */
-    std::vector<double> linkCom;       /**< [n+1][3]   */
-    std::vector<double> linkInertia;   /**< [n+1][9]   */
-    std::vector<int32_t> frameLink;    /**< [F]        */
-    std::vector<double> framePose;     /**< [F][12]    */
-    /** [n] or empty: 1 marks a fixed joint (a URDF "fixed" joint, no DoF). setRobotModel merges
-     *  each fixed joint's child link into its parent (reduceFixedJoints), as iDynTree's model has
-     *  no DoF for it; the state and torque vectors then cover the remaining joints only. */
-    std::vector<uint8_t> fixedJoint;
-    /** [n] or empty (every joint revolute): BLF_JOINT_REVOLUTE / BLF_JOINT_PRISMATIC (the child
-     *  link slides along the joint axis by q, URDF "prismatic"). */
-    std::vector<int32_t> jointType;
-    /** [n] or empty (no limits): the joints' position range, -inf / +inf where a side has none, and
-     *  their velocity limit (+inf: none).  blf::loadUrdf fills them from <limit>; the IK's
-     *  JointLimitsTask reads them with "use_model_limits".  The dynamics do not use them. */
-    std::vector<double> jointLower, jointUpper, jointVelocityLimit;
-};
-
-/** The model with every joint marked in model.fixedJoint removed and its child link merged into
- *  the parent link (mass, COM, inertia by the parallel-axis theorem; child joints and frames
- *  re-expressed in the parent link's frame at q = 0), deepest first.  The result has an empty
- *  fixedJoint.  Its rigid-body terms equal the full model's with the fixed joints held at
- *  q = 0, q_dot = 0 (blf/robot.py reduce_fixed_joints, tests/test_fb_dynamics.py). */
-RobotModel reduceFixedJoints(const RobotModel& model);
-/** Whether reduceFixedJoints can merge `model`: consistent array sizes (fixedJoint of ndof
- *  entries), joints in topological order (parent[j] <= j), frames on existing links.  A model that
- *  fails this comes back from reduceFixedJoints unchanged. */
-bool fixedJointMergeable(const RobotModel& model);
-} // namespace blf
 
 namespace BipedalLocomotion
 {
@@ -87,11 +47,9 @@ class FloatingBaseDynamicalSystem
     std::size_t m_actuatedDoFs{0};
     double m_rho{0.01};
     blf::Vector3 m_gravity{{0.0, 0.0, -9.81}};
-    bool m_hasModel{false};
     bool m_useMassMatrixRegularizationTerm{false};
-    blf::RobotModel m_model;
-    blf::DeviceBuffer<int32_t> m_dParent, m_dFrameLink, m_dContactFrame, m_dJointType, m_dContactLaw;
-    blf::DeviceBuffer<double> m_dOrigin, m_dRot, m_dAxis, m_dMass, m_dCom, m_dInertia, m_dFramePose;
+    blf::DeviceRobotModel m_model;
+    blf::DeviceBuffer<int32_t> m_dContactFrame, m_dContactLaw;
     blf::DeviceBuffer<double> m_dReg, m_dState, m_dTau, m_dContactParams, m_dNullPose, m_dOut;
     blf::DeviceBuffer<double> m_dContactWrench, m_dFrameOut;
     blf::DeviceBuffer<double> m_dIdIn, m_dIdOut;   // inverseDynamics: joint accelerations | torques, base acceleration
@@ -107,7 +65,9 @@ class FloatingBaseDynamicalSystem
 public:
     bool initalize(std::weak_ptr<ParametersHandler::IParametersHandler> handler) final;
     void setGravityVector(const blf::Vector3& gravity) { m_gravity = gravity; }
-    /** Replaces setKinDyn(): the robot model whose rigid-body terms the device computes. */
+    /** Replaces setKinDyn(): the robot model whose rigid-body terms the device computes.  False,
+     *  before any device work and with blf::describe's line, for a model blf::prepareRobotModel
+     *  refuses (blf/robot_model.h); the model set before stays. */
     bool setRobotModel(const blf::RobotModel& model);
     bool setMassMatrixRegularization(const blf::MatrixXd& matrix);
     bool dynamics(const double& time, StateDerivativeType& stateDerivative) final;

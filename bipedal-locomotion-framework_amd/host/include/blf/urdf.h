@@ -28,7 +28,7 @@
 #include <string>
 #include <vector>
 
-#include <BipedalLocomotion/System/FloatingBaseSystemDynamics.h>
+#include <blf/robot_model.h>
 
 namespace blf
 {

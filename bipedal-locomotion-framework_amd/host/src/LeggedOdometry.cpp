@@ -18,6 +18,7 @@ namespace
 // detection is bypassed: no force reaches the kernel's triggers (see setContactStatus), so their
 // parameters are never used; they only have to be ones the call accepts
 const double kUnusedParams[4] = {1.0, 0.0, 0.0, 0.0};
+const double kGravity[3] = {0.0, 0.0, -9.81};
 
 bool fail(const char* where, const std::string& what)
 {
@@ -47,23 +48,10 @@ bool LeggedOdometry::setRobotModel(const blf::RobotModel& fullModel, const std::
 {
     const char* where = "setRobotModel";
     if (m_state == State::NotInitialized) return fail(where, "Call initialize() first.");
-    if (!fullModel.fixedJoint.empty() && !blf::fixedJointMergeable(fullModel))
-        return fail(where, "Corrupted robot model.");
-    const blf::RobotModel model = fullModel.fixedJoint.empty() ? fullModel : blf::reduceFixedJoints(fullModel);
-    const std::size_t n = static_cast<std::size_t>(model.ndof < 0 ? 0 : model.ndof), F = model.frameLink.size();
-    if (model.ndof < 1 || model.ndof > BLF_FBD_MAX_DOFS || model.parent.size() != n || model.jointOrigin.size() != 3 * n
-        || model.jointRotation.size() != 9 * n || model.jointAxis.size() != 3 * n || model.linkMass.size() != n + 1
-        || model.linkCom.size() != 3 * (n + 1) || model.linkInertia.size() != 9 * (n + 1)
-        || model.framePose.size() != 12 * F || (!model.jointType.empty() && model.jointType.size() != n))
-        return fail(where, "Corrupted robot model.");
-    for (std::size_t j = 0; j < n; ++j)
-        if (model.parent[j] < 0 || model.parent[j] > static_cast<int32_t>(j))
-            return fail(where, "The joints must be in topological order (parent[j] <= j).");
-    for (const int32_t t : model.jointType)
-        if (t != BLF_JOINT_REVOLUTE && t != BLF_JOINT_PRISMATIC)
-            return fail(where, "Unknown joint type " + std::to_string(t) + ".");
-    for (const int32_t l : model.frameLink)
-        if (l < 0 || l > model.ndof) return fail(where, "A frame is attached to a link the model does not have.");
+    blf::RobotModel model;
+    const blf::ModelDefect defect = blf::prepareRobotModel(fullModel, model);
+    if (defect != blf::ModelDefect::None) return fail(where, blf::describe(defect, model));
+    const std::size_t n = static_cast<std::size_t>(model.ndof), F = model.frameLink.size();
     if (F < 1 || F > BLF_ODOM_MAX_CONTACTS)
         return fail(where, std::to_string(F) + " frames: every frame is a contact slot, 1 to "
                                + std::to_string(BLF_ODOM_MAX_CONTACTS) + " are supported.");
@@ -74,12 +62,7 @@ bool LeggedOdometry::setRobotModel(const blf::RobotModel& fullModel, const std::
     const auto it = std::find(names.begin(), names.end(), m_initialFixedFrame);
     if (it == names.end()) return fail(where, "The model has no frame named " + m_initialFixedFrame + ".");
     if (blf::threadHandle() == nullptr) return fail(where, "No device.");
-    if (!(m_dParent.upload(model.parent) && m_dOrigin.upload(model.jointOrigin) && m_dRot.upload(model.jointRotation)
-          && m_dAxis.upload(model.jointAxis) && m_dMass.upload(model.linkMass) && m_dCom.upload(model.linkCom)
-          && m_dInertia.upload(model.linkInertia) && m_dFrameLink.upload(model.frameLink)
-          && m_dFramePose.upload(model.framePose) && (model.jointType.empty() || m_dJointType.upload(model.jointType))))
-        return fail(where, "The model could not be copied to the device.");
-    m_model = model;
+    if (!m_model.set(model)) return fail(where, "The model could not be copied to the device.");
     m_names = names;
     m_fixed = static_cast<int>(it - names.begin());
     m_fixedPose = blf::Transform::Identity();   // the world starts at the initial fixed frame
@@ -123,29 +106,6 @@ bool LeggedOdometry::setContactStatus(const std::string& name, bool contactStatu
     return true;
 }
 
-// the blf_fb_model over the device copies
-static blf_fb_model deviceModel(const blf::RobotModel& m, const int32_t* parent, const double* origin, const double* rot,
-                                const double* axis, const double* mass, const double* com, const double* inertia,
-                                const int32_t* frameLink, const double* framePose, const int32_t* jointType)
-{
-    blf_fb_model d{};
-    d.ndof = m.ndof;
-    d.nframes = static_cast<int32_t>(m.frameLink.size());
-    d.parent = parent;
-    d.joint_origin = origin;
-    d.joint_rot = rot;
-    d.joint_axis = axis;
-    d.link_mass = mass;
-    d.link_com = com;
-    d.link_inertia = inertia;
-    d.frame_link = frameLink;
-    d.frame_pose = framePose;
-    d.gravity[2] = -9.81;
-    d.rho = 0.0;
-    d.joint_type = m.jointType.empty() ? nullptr : jointType;
-    return d;
-}
-
 bool LeggedOdometry::advance()
 {
     const char* where = "advance";
@@ -171,9 +131,7 @@ bool LeggedOdometry::advance()
     std::copy(m_trigState.begin(), m_trigState.end(), ints.begin() + K);
     ints[2 * K] = m_fixed;
     if (!m_dData.upload(data) || !m_dInts.upload(ints)) return fail(where, "The inputs could not be copied to the device.");
-    const blf_fb_model dm = deviceModel(m_model, m_dParent.data(), m_dOrigin.data(), m_dRot.data(), m_dAxis.data(),
-                                        m_dMass.data(), m_dCom.data(), m_dInertia.data(), m_dFrameLink.data(),
-                                        m_dFramePose.data(), m_dJointType.data());
+    const blf_fb_model dm = m_model.view(kGravity, 0.0);
     double* d = m_dData.data();
     int32_t* i = m_dInts.data();
     if (!blf::report(blf_legged_odometry_advance(h, &dm, static_cast<int32_t>(K), i, kUnusedParams, 1, d, d + oQ, d + oDq,
@@ -205,28 +163,23 @@ bool LeggedOdometry::changeFixedFrame(const std::string& name)
     if (h == nullptr) return fail(where, "No device.");
     // the frame's world pose at the last estimate: blf_fb_frame_state at (basePose, q)
     const std::size_t n = m_q.size();
-    std::vector<double> st(18 + 2 * n + 12, 0.0);   // base vel 6 | joint vel n | base pos 3 | base rot 9 | joint pos n | pose 12
-    for (int k = 0; k < 3; ++k) st[6 + n + k] = m_output.basePose.position[k];
-    for (int k = 0; k < 9; ++k) st[9 + n + k] = m_output.basePose.rotation[k];
-    std::copy(m_q.begin(), m_q.end(), st.begin() + 18 + n);
+    const std::size_t oPose = blf::fbStateSize(n);
+    std::vector<double> st(oPose + 12, 0.0);   // the state, its velocities zero | pose 12
+    const blf_fb_state hs = blf::fbStateAt(st.data(), n);
+    std::copy(m_output.basePose.position.begin(), m_output.basePose.position.end(), hs.base_pos);
+    std::copy(m_output.basePose.rotation.begin(), m_output.basePose.rotation.end(), hs.base_rot);
+    std::copy(m_q.begin(), m_q.end(), hs.joint_pos);
     std::vector<int32_t> frame(1, c);
     if (!m_dData.upload(st) || !m_dInts.upload(frame)) return fail(where, "The inputs could not be copied to the device.");
-    const blf_fb_model dm = deviceModel(m_model, m_dParent.data(), m_dOrigin.data(), m_dRot.data(), m_dAxis.data(),
-                                        m_dMass.data(), m_dCom.data(), m_dInertia.data(), m_dFrameLink.data(),
-                                        m_dFramePose.data(), m_dJointType.data());
+    const blf_fb_model dm = m_model.view(kGravity, 0.0);
     double* d = m_dData.data();
-    blf_fb_state s{};
-    s.base_vel = d;
-    s.joint_vel = d + 6;
-    s.base_pos = d + 6 + n;
-    s.base_rot = d + 9 + n;
-    s.joint_pos = d + 18 + n;
-    if (!blf::report(blf_fb_frame_state(h, &dm, &s, 1, m_dInts.data(), 1, d + 18 + 2 * n, nullptr, nullptr),
+    const blf_fb_state s = blf::fbStateAt(d, n);
+    if (!blf::report(blf_fb_frame_state(h, &dm, &s, 1, m_dInts.data(), 1, d + oPose, nullptr, nullptr),
                      "LeggedOdometry::changeFixedFrame"))
         return false;
     if (!m_dData.download(st.data(), st.size())) return fail(where, "The pose could not be copied from the device.");
-    for (int k = 0; k < 3; ++k) m_fixedPose.position[k] = st[18 + 2 * n + k];
-    for (int k = 0; k < 9; ++k) m_fixedPose.rotation[k] = st[18 + 2 * n + 3 + k];
+    for (int k = 0; k < 3; ++k) m_fixedPose.position[k] = st[oPose + k];
+    for (int k = 0; k < 9; ++k) m_fixedPose.rotation[k] = st[oPose + 3 + k];
     m_fixed = c;
     return true;
 }

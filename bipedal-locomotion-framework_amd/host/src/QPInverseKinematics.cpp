@@ -52,57 +52,26 @@ bool QPInverseKinematics::setRobotModel(const blf::RobotModel& fullModel,
         std::cerr << where << "The problem is already finalized." << std::endl;
         return false;
     }
-    if (!fullModel.fixedJoint.empty() && !blf::fixedJointMergeable(fullModel))
+    blf::RobotModel model;
+    const blf::ModelDefect defect = blf::prepareRobotModel(fullModel, model);
+    if (defect != blf::ModelDefect::None)
     {
-        std::cerr << where << "Corrupted robot model." << std::endl;
+        std::cerr << where << blf::describe(defect, model) << std::endl;
         return false;
     }
-    const blf::RobotModel model = fullModel.fixedJoint.empty() ? fullModel : blf::reduceFixedJoints(fullModel);
-    const std::size_t n = static_cast<std::size_t>(model.ndof < 0 ? 0 : model.ndof);
-    const std::size_t F = model.frameLink.size();
-    if (model.ndof < 1 || model.ndof > BLF_FBD_MAX_DOFS || model.parent.size() != n
-        || model.jointOrigin.size() != 3 * n || model.jointRotation.size() != 9 * n
-        || model.jointAxis.size() != 3 * n || model.linkMass.size() != n + 1
-        || model.linkCom.size() != 3 * (n + 1) || model.linkInertia.size() != 9 * (n + 1)
-        || model.framePose.size() != 12 * F || (!model.jointType.empty() && model.jointType.size() != n)
-        || (!frameNames.empty() && frameNames.size() != F)
-        || model.jointLower.size() != model.jointUpper.size()
-        || (!model.jointLower.empty() && model.jointLower.size() != n))
+    if (!frameNames.empty() && frameNames.size() != model.frameLink.size())
     {
-        std::cerr << where << "Corrupted robot model." << std::endl;
+        std::cerr << where << frameNames.size() << " frame names for " << model.frameLink.size() << " frames."
+                  << std::endl;
         return false;
     }
-    for (std::size_t j = 0; j < n; ++j)
-        if (model.parent[j] < 0 || model.parent[j] > static_cast<int32_t>(j))
-        {
-            std::cerr << where << "The joints must be in topological order (parent[j] <= j)." << std::endl;
-            return false;
-        }
-    for (const int32_t l : model.frameLink)
-        if (l < 0 || l > model.ndof)
-        {
-            std::cerr << where << "A frame is attached to an unknown link." << std::endl;
-            return false;
-        }
-    for (const int32_t t : model.jointType)
-        if (t != BLF_JOINT_REVOLUTE && t != BLF_JOINT_PRISMATIC)
-        {
-            std::cerr << where << "Unknown joint type " << t << "." << std::endl;
-            return false;
-        }
     if (blf::threadHandle() == nullptr)
     {
         std::cerr << where << "No device." << std::endl;
         return false;
     }
-    m_model = model;
     m_frameNames = frameNames;
-    m_hasModel = m_dParent.upload(model.parent) && m_dOrigin.upload(model.jointOrigin)
-                 && m_dRot.upload(model.jointRotation) && m_dAxis.upload(model.jointAxis)
-                 && m_dMass.upload(model.linkMass) && m_dCom.upload(model.linkCom)
-                 && m_dInertia.upload(model.linkInertia) && m_dFrameLink.upload(model.frameLink)
-                 && m_dFramePose.upload(model.framePose)
-                 && (model.jointType.empty() || m_dJointType.upload(model.jointType));
+    m_hasModel = m_model.set(model);
     return m_hasModel;
 }
 
@@ -115,7 +84,7 @@ bool QPInverseKinematics::setRobotState(const blf::Vector3& basePosition, const 
                   << std::endl;
         return false;
     }
-    if (jointPositions.size() != static_cast<std::size_t>(m_model.ndof))
+    if (jointPositions.size() != static_cast<std::size_t>(m_model.host().ndof))
     {
         std::cerr << "[QPInverseKinematics::setRobotState] Wrong size of the vectors." << std::endl;
         return false;
@@ -308,7 +277,7 @@ bool QPInverseKinematics::finalize()
             const auto it = std::find(m_frameNames.begin(), m_frameNames.end(), se3.frameName());
             index = it == m_frameNames.end() ? -1 : static_cast<int>(it - m_frameNames.begin());
         }
-        if (index < 0 || index >= static_cast<int>(m_model.frameLink.size()))
+        if (index < 0 || index >= static_cast<int>(m_model.host().frameLink.size()))
         {
             std::cerr << where << "The frame of the task " << e.name << " does not exist in the model."
                       << std::endl;
@@ -316,7 +285,7 @@ bool QPInverseKinematics::finalize()
         }
         frames.push_back(index);
     }
-    if (m_jointTask >= 0 && m_tasks[m_jointTask].weight.size() != static_cast<std::size_t>(m_model.ndof))
+    if (m_jointTask >= 0 && m_tasks[m_jointTask].weight.size() != static_cast<std::size_t>(m_model.host().ndof))
     {
         std::cerr << where << "The joint tracking task's weight must have one entry per joint." << std::endl;
         return false;
@@ -325,21 +294,21 @@ bool QPInverseKinematics::finalize()
     if (m_limitsTask >= 0)
     {
         const auto& lt = static_cast<const JointLimitsTask&>(*m_tasks[m_limitsTask].task);
-        const std::size_t n = static_cast<std::size_t>(m_model.ndof);
+        const std::size_t n = static_cast<std::size_t>(m_model.host().ndof);
         if (!lt.isValid() || lt.klim().size() != n)
         {
             std::cerr << where << "The joint limits task " << m_tasks[m_limitsTask].name << " is not initialized "
                       << "or has " << lt.klim().size() << " joints, the model " << n << "." << std::endl;
             return false;
         }
-        if (lt.useModelLimits() && m_model.jointLower.size() != n)
+        if (lt.useModelLimits() && m_model.host().jointLower.size() != n)
         {
             std::cerr << where << "The joint limits task asks for the model's limits and the model has none."
                       << std::endl;
             return false;
         }
-        const std::vector<double>& lo = lt.useModelLimits() ? m_model.jointLower : lt.lowerLimits();
-        const std::vector<double>& up = lt.useModelLimits() ? m_model.jointUpper : lt.upperLimits();
+        const std::vector<double>& lo = lt.useModelLimits() ? m_model.host().jointLower : lt.lowerLimits();
+        const std::vector<double>& up = lt.useModelLimits() ? m_model.host().jointUpper : lt.upperLimits();
         limits.insert(limits.end(), lo.begin(), lo.end());
         limits.insert(limits.end(), up.begin(), up.end());
         limits.insert(limits.end(), lt.klim().begin(), lt.klim().end());
@@ -382,7 +351,7 @@ bool QPInverseKinematics::advance()
                       << std::endl;
             return false;
         }
-    const std::size_t n = static_cast<std::size_t>(m_model.ndof), NV = n + 6, K = m_frames.size();
+    const std::size_t n = static_cast<std::size_t>(m_model.host().ndof), NV = n + 6, K = m_frames.size();
     const auto& jt = static_cast<const JointTrackingTask&>(*m_tasks[m_jointTask].task);
     if (jt.kp().size() != n || jt.position().size() != n)
     {
@@ -390,14 +359,12 @@ bool QPInverseKinematics::advance()
                   << "." << std::endl;
         return false;
     }
-    const std::size_t oState = NV, oW = oState + 18 + 2 * n, oKp = oW + 6 * K, oPose = oKp + 2 * K,
+    const std::size_t oState = NV, oW = oState + blf::fbStateSize(n), oKp = oW + 6 * K, oPose = oKp + 2 * K,
                       oTwist = oPose + 12 * K, oCw = oTwist + 6 * K, oCp = oCw + 3, oCv = oCp + 3,
                       oJw = oCv + 3, oJk = oJw + n, oJp = oJk + n, oJv = oJp + n, total = oJv + n;
     std::vector<double> host(total, 0.0);
-    double* st = host.data() + oState;
-    for (int i = 0; i < 3; ++i) st[6 + n + i] = m_basePosition[i];
-    for (int i = 0; i < 9; ++i) st[9 + n + i] = m_baseRotation[i];
-    for (std::size_t i = 0; i < n; ++i) st[18 + n + i] = m_jointPositions[i];
+    blf::fbStatePack(blf::Vector6{}, blf::VectorXd(n), m_basePosition, m_baseRotation, m_jointPositions,
+                     host.data() + oState);   // the velocities are not read
     std::size_t k = 0;
     for (const Entry& e : m_tasks)
     {
@@ -438,23 +405,9 @@ bool QPInverseKinematics::advance()
     if (!m_dData.upload(host) || !m_dInt.upload(ints)) return false;
 
     double* d = m_dData.data();
-    m_cModel = blf_fb_model{};
-    m_cModel.ndof = m_model.ndof;
-    m_cModel.nframes = static_cast<int32_t>(m_model.frameLink.size());
-    m_cModel.parent = m_dParent.data();
-    m_cModel.joint_origin = m_dOrigin.data();
-    m_cModel.joint_rot = m_dRot.data();
-    m_cModel.joint_axis = m_dAxis.data();
-    m_cModel.link_mass = m_dMass.data();
-    m_cModel.link_com = m_dCom.data();
-    m_cModel.link_inertia = m_dInertia.data();
-    m_cModel.frame_link = m_dFrameLink.data();
-    m_cModel.frame_pose = m_dFramePose.data();
-    m_cModel.gravity[2] = -9.81;
-    m_cModel.rho = 0.01;
-    m_cModel.joint_type = m_model.jointType.empty() ? nullptr : m_dJointType.data();
-    m_cState = blf_fb_state{d + oState, d + oState + 6, d + oState + 6 + n, d + oState + 9 + n,
-                            d + oState + 18 + n};
+    const double gravity[3] = {0.0, 0.0, -9.81};
+    m_cModel = m_model.view(gravity, 0.01);
+    m_cState = blf::fbStateAt(d + oState, n);
     m_cTasks = blf_ik_tasks{};
     m_cTasks.nse3 = static_cast<int32_t>(K);
     m_cTasks.frame = m_dInt.data();

@@ -14,6 +14,7 @@
 #include <memory>
 #include <sstream>
 
+#include <blf/robot_model.h>
 #include <blf/urdf.h>
 
 namespace

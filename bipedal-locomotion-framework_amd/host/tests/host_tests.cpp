@@ -36,6 +36,7 @@
 #include <BipedalLocomotion/System/VariablesHandler.h>
 #include <blf/urdf.h>
 
+#include "model_fixtures.h"
 #include "test_harness.h"
 
 using namespace BipedalLocomotion;
@@ -1069,25 +1070,6 @@ static void testIntegratorKinematicsLiteral()
 }
 
 // ---- FloatingBaseDynamicalSystem (FloatingBaseSystemDynamics.cpp:102-251) on a 3-joint chain ---
-static blf::RobotModel chainModel()
-{
-    blf::RobotModel m;
-    m.ndof = 3;
-    m.parent = {0, 1, 2};
-    m.jointOrigin = {0.0, 0.0, -0.1, 0.0, 0.0, -0.3, 0.0, 0.0, -0.3};
-    m.jointRotation.clear();
-    for (int j = 0; j < 3; ++j) m.jointRotation.insert(m.jointRotation.end(), {1, 0, 0, 0, 1, 0, 0, 0, 1});
-    m.jointAxis = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 1.0, 0.0};
-    m.linkMass = {5.0, 2.0, 1.5, 1.0};
-    m.linkCom = {0.0, 0.0, 0.0, 0.0, 0.0, -0.15, 0.0, 0.0, -0.15, 0.05, 0.0, -0.02};
-    m.linkInertia.clear();
-    for (double mass : m.linkMass)
-        m.linkInertia.insert(m.linkInertia.end(), {0.01 * mass, 0, 0, 0, 0.012 * mass, 0, 0, 0, 0.008 * mass});
-    m.frameLink = {3};
-    m.framePose = {0.02, 0.0, -0.05, 1, 0, 0, 0, 1, 0, 0, 0, 1};
-    return m;
-}
-
 static void testFloatingBaseDynamics()
 {
     auto system = std::make_shared<FloatingBaseDynamicalSystem>();
