@@ -700,115 +700,6 @@ __global__ __launch_bounds__(64) void fbd_dynamics_kernel(Model m, blf_fb_state 
     for (int j = lane; j < n; j += HW) out.joint_pos[(int64_t)n * q + j] = loc[6 + j];
 }
 
-// The joint impedance of blf_fbd_euler_integrate_impedance: tau = kp (q_ref - q) - kd qdot, set as
-// the control input before every Euler step (kp == nullptr: the constant torques `tau`).
-struct Impedance {
-    const double *kp, *kd, *qref;
-};
-
-template <int NVMAX, int HW, bool PRI, bool ABA>
-// Two systems per wavefront (HW = 32) keep more state live per wave: capping it at 256 VGPRs for
-// two waves per SIMD spills (9.40 ms per c5 period), one wave per SIMD does not (8.29 ms, against
-// 9.29 ms with one system per wavefront at two waves per SIMD; tools/ab_c5.sh).
-__global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m, blf_fb_state st,
-                                                          const double* __restrict__ tau,
-                                                          Contacts ct, const double* reg,
-                                                          int32_t nsteps, double dT, double dT_last,
-                                                          Impedance imp, int64_t batch)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const Half<HW> H;
-    const int n = m.n, NV = n + 6;
-    // the per-system constants of the Euler loop staged in LDS: the two-systems form only (LLVM's
-    // allocator crashes on the HW = 64 form)
-    constexpr bool kCS = HW == 32;
-    const Smem S(smem + H.half * Smem(nullptr, n, ct.C, ABA).total, n, ct.C, ABA);
-    const int lane = H.hl;
-    constexpr int per = kWave / HW;   // systems per wavefront
-    const Topo T = build_topo<HW>(m, S);
-    double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n | dR 9
-    double* dR = loc + 18 + 2 * n;
-    const int64_t i0 = (int64_t)blockIdx.x * per + H.half;
-    // a system past the end of an odd batch is computed (as the last system's copy, beside its
-    // partner) and written nowhere
-    const bool active = i0 < batch;   // see fbd_dynamics_kernel
-    const int64_t q = active ? i0 : batch - 1;
-    for (int i = lane; i < 18 + 2 * n; i += HW) {
-        double v;
-        if (i < 6) v = st.base_vel[6 * q + i];
-        else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
-        else if (i < 9 + n) {   // the reference point; the position relative to it starts at zero
-            loc[kRef(n) + (i - 6 - n)] = st.base_pos[3 * q + (i - 6 - n)];
-            v = 0.0;
-        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
-        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
-        loc[i] = v;
-    }
-    if constexpr (kCS) {   // this system's constants of the Euler loop, once (Smem o_cst / o_imp)
-        const int C = ct.C;
-        for (int i = lane; i < 29 * C; i += HW) {
-            double v;
-            if (i < C) v = (double)m.flink[ct.frame[i]];
-            else if (i < 13 * C) v = m.fpose[12 * ct.frame[(i - C) / 12] + (i - C) % 12];
-            else if (i < 25 * C) {   // null poses, their positions relative to the reference point
-                const int e = (i - 13 * C) % 12;
-                v = ct.null_pose[(q * C) * 12 + (i - 13 * C)];
-                if (e < 3) v = v - st.base_pos[3 * q + e];
-            }
-            else v = ct.params[i - 25 * C];
-            S.cst()[i] = v;
-        }
-        if (imp.kp)
-            for (int j = lane; j < n; j += HW) {
-                S.imp()[j] = imp.kp[j];
-                S.imp()[n + j] = imp.kd[j];
-                S.imp()[2 * n + j] = imp.qref[(int64_t)n * q + j];
-            }
-    }
-    wave_sync();
-    bool ok = true;
-    const double* tq = tau + (int64_t)n * q;
-    for (int32_t step = 0; step < nsteps; ++step) {
-        const double h = step + 1 < nsteps ? dT : dT_last;
-        if (imp.kp) {   // the control input of this step from its start state
-            for (int j = lane; j < n; j += HW) {
-                if constexpr (kCS)
-                    S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * loc[6 + j];
-                else
-                    S.tq()[j] = imp.kp[j] * (imp.qref[(int64_t)n * q + j] - loc[18 + n + j]) - imp.kd[j] * loc[6 + j];
-            }
-            wave_sync();
-            tq = S.tq();
-        }
-        ok = fbd_eval<NVMAX, HW, PRI, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
-                                                tq, ct, q, reg, T, loc + kRef(n)) && ok;
-        if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, loc + 3, dR);
-        wave_sync();
-        // every element moves by its derivative at the start of the step (ForwardEuler.tpp:37-45):
-        // positions first (they read the old velocities), then the velocities
-        for (int i = lane; i < 12 + n; i += HW) {
-            // base position (3), base rotation (9), joint positions (n)
-            if (i < 3) loc[6 + n + i] = loc[6 + n + i] + loc[i] * h;
-            else if (i < 12) loc[6 + n + i] = loc[6 + n + i] + dR[i - 3] * h;
-            else loc[18 + n + (i - 12)] = loc[18 + n + (i - 12)] + loc[6 + (i - 12)] * h;
-        }
-        wave_sync();
-        for (int i = lane; i < NV; i += HW) loc[i] = loc[i] + S.rhs()[i] * h;
-        wave_sync();
-    }
-    if (active) {
-        const double nan = __builtin_nan("");
-        for (int i = lane; i < 18 + 2 * n; i += HW) {
-            const double v = ok ? loc[i] : nan;
-            if (i < 6) st.base_vel[6 * q + i] = v;
-            else if (i < 6 + n) st.joint_vel[(int64_t)n * q + (i - 6)] = v;
-            else if (i < 9 + n) st.base_pos[3 * q + (i - 6 - n)] = loc[kRef(n) + (i - 6 - n)] + v;
-            else if (i < 18 + n) st.base_rot[9 * q + (i - 9 - n)] = v;
-            else st.joint_pos[(int64_t)n * q + (i - 18 - n)] = v;
-        }
-    }
-}
-
 // The closed loop's state -> plan map: the centre of mass, its velocity
 // and the DCM of every system,
 //   c = sum_l m_l (p_l + R_l com_l) / m,   cdot = sum_l m_l (v_l + w_l x R_l com_l) / m,
@@ -958,137 +849,6 @@ __global__ __launch_bounds__(256) void com_reference_kernel(const double* __rest
     }
     cref[2 * q + a] = c;
     if (xiend) xiend[2 * q + a] = xi;
-}
-
-// blf_fbd_euler_integrate_impedance_traj: fbd_euler_kernel's impedance form with the reference
-// indexed by the integration step, slice s(i) = min(i / sps, T - 1) of qref [T][B][n], a velocity
-// feed-forward qdref (or null) and a per-system bias qbias (or null):
-//   r = qref (+ qbias),  tau = kp (r - q) - kd (qdot - qdref)   (qdref null: - kd qdot)
-struct ImpedanceTraj {
-    const double *kp, *kd, *qref, *qdref, *qbias;
-    int64_t qdstride;
-    int32_t T, sps;
-};
-
-// Text of its own beside fbd_euler_kernel (whose instantiations keep their assembly): the same
-// staging, step and write-back, and the torque block replaced.  Two systems per wavefront: r and
-// qdref of the current slice sit in LDS (r in Smem's q_ref slot, qdref in n doubles behind
-// Smem::total) and are restaged only at a step where the slice changes; one system per wavefront
-// reads them from global memory every step, as the held form reads imp.qref.
-template <int NVMAX, int HW, bool PRI, bool ABA>
-__global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_traj_kernel(Model m, blf_fb_state st,
-                                                          Contacts ct, const double* reg,
-                                                          int32_t nsteps, double dT, double dT_last,
-                                                          ImpedanceTraj imp, int64_t batch)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const Half<HW> H;
-    const int n = m.n, NV = n + 6;
-    constexpr bool kCS = HW == 32;
-    const int nx = kCS ? (n + 1) & ~1 : 0;   // the slice's qdref behind the system's Smem block
-    const Smem S(smem + H.half * (Smem(nullptr, n, ct.C, ABA).total + nx), n, ct.C, ABA);
-    double* const qdr = S.base + S.total;
-    const int lane = H.hl;
-    constexpr int per = kWave / HW;
-    const Topo T = build_topo<HW>(m, S);
-    double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n | dR 9
-    double* dR = loc + 18 + 2 * n;
-    const int64_t i0 = (int64_t)blockIdx.x * per + H.half;
-    const bool active = i0 < batch;   // see fbd_euler_kernel
-    const int64_t q = active ? i0 : batch - 1;
-    for (int i = lane; i < 18 + 2 * n; i += HW) {
-        double v;
-        if (i < 6) v = st.base_vel[6 * q + i];
-        else if (i < 6 + n) v = st.joint_vel[(int64_t)n * q + (i - 6)];
-        else if (i < 9 + n) {   // the reference point; the position relative to it starts at zero
-            loc[kRef(n) + (i - 6 - n)] = st.base_pos[3 * q + (i - 6 - n)];
-            v = 0.0;
-        } else if (i < 18 + n) v = st.base_rot[9 * q + (i - 9 - n)];
-        else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
-        loc[i] = v;
-    }
-    if constexpr (kCS) {
-        const int C = ct.C;
-        for (int i = lane; i < 29 * C; i += HW) {
-            double v;
-            if (i < C) v = (double)m.flink[ct.frame[i]];
-            else if (i < 13 * C) v = m.fpose[12 * ct.frame[(i - C) / 12] + (i - C) % 12];
-            else if (i < 25 * C) {   // null poses, their positions relative to the reference point
-                const int e = (i - 13 * C) % 12;
-                v = ct.null_pose[(q * C) * 12 + (i - 13 * C)];
-                if (e < 3) v = v - st.base_pos[3 * q + e];
-            }
-            else v = ct.params[i - 25 * C];
-            S.cst()[i] = v;
-        }
-        for (int j = lane; j < n; j += HW) {
-            S.imp()[j] = imp.kp[j];
-            S.imp()[n + j] = imp.kd[j];
-        }
-    }
-    wave_sync();
-    bool ok = true;
-    int32_t slice = -1, left = 0;   // the slice in use and the steps it still holds
-    for (int32_t step = 0; step < nsteps; ++step) {
-        const double h = step + 1 < nsteps ? dT : dT_last;
-        const bool next = left == 0 && slice + 1 < imp.T;   // the last slice is held to the end
-        if (next) {
-            ++slice;
-            left = imp.sps;
-        }
-        --left;
-        const int64_t at = (int64_t)slice * batch + q;   // element (slice, q, .)
-        if constexpr (kCS) {
-            if (next)
-                for (int j = lane; j < n; j += HW) {
-                    double r = imp.qref[at * n + j];
-                    if (imp.qbias) r = r + imp.qbias[(int64_t)n * q + j];
-                    S.imp()[2 * n + j] = r;
-                    if (imp.qdref) qdr[j] = imp.qdref[at * imp.qdstride + j];
-                }
-        }
-        // the control input of this step from its start state
-        for (int j = lane; j < n; j += HW) {
-            if constexpr (kCS) {
-                if (imp.qdref)
-                    S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * (loc[6 + j] - qdr[j]);
-                else
-                    S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * loc[6 + j];
-            } else {
-                double r = imp.qref[at * n + j];
-                if (imp.qbias) r = r + imp.qbias[(int64_t)n * q + j];
-                if (imp.qdref)
-                    S.tq()[j] = imp.kp[j] * (r - loc[18 + n + j]) - imp.kd[j] * (loc[6 + j] - imp.qdref[at * imp.qdstride + j]);
-                else
-                    S.tq()[j] = imp.kp[j] * (r - loc[18 + n + j]) - imp.kd[j] * loc[6 + j];
-            }
-        }
-        wave_sync();
-        ok = fbd_eval<NVMAX, HW, PRI, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
-                                                S.tq(), ct, q, reg, T, loc + kRef(n)) && ok;
-        if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, loc + 3, dR);
-        wave_sync();
-        // positions first (they read the old velocities), then the velocities: fbd_euler_kernel
-        for (int i = lane; i < 12 + n; i += HW) {
-            if (i < 3) loc[6 + n + i] = loc[6 + n + i] + loc[i] * h;
-            else if (i < 12) loc[6 + n + i] = loc[6 + n + i] + dR[i - 3] * h;
-            else loc[18 + n + (i - 12)] = loc[18 + n + (i - 12)] + loc[6 + (i - 12)] * h;
-        }
-        wave_sync();
-        for (int i = lane; i < NV; i += HW) loc[i] = loc[i] + S.rhs()[i] * h;
-        wave_sync();
-    }
-    if (active) {
-        const double nan = __builtin_nan("");
-        for (int i = lane; i < 18 + 2 * n; i += HW) {
-            const double v = ok ? loc[i] : nan;
-            if (i < 6) st.base_vel[6 * q + i] = v;
-            else if (i < 6 + n) st.joint_vel[(int64_t)n * q + (i - 6)] = v;
-            else if (i < 9 + n) st.base_pos[3 * q + (i - 6 - n)] = loc[kRef(n) + (i - 6 - n)] + v;
-            else if (i < 18 + n) st.base_rot[9 * q + (i - 9 - n)] = v;
-            else st.joint_pos[(int64_t)n * q + (i - 18 - n)] = v;
-        }
-    }
 }
 
 // ---- Inverse dynamics (blf_fb_inverse_dynamics, blf_c.h section 8b): the hybrid form, joint
@@ -1442,40 +1202,88 @@ __global__ __launch_bounds__(64) void fb_invdyn_kernel(Model m, blf_fb_state st,
     if (status && lane == 0) status[q] = bad ? BLF_IK_BAD_INPUT : pos ? BLF_IK_OK : BLF_IK_NOT_POSITIVE;
 }
 
-// blf_fbd_euler_integrate_computed_torque_traj: fbd_euler_traj_kernel's schedule, slices, step and
-// write-back with the torque law replaced by the inverse dynamics of the commanded acceleration,
+// ---- The Euler kernel's three torque laws.  A law is a kernel argument and the kernel's last template
+//      parameter; Reg is the type of the kernel's mass-matrix regularisation argument under that law.
+
+// blf_fbd_euler_integrate_impedance: the joint impedance tau = kp (q_ref - q) - kd qdot, set as the
+// control input before every Euler step (kp == nullptr: the constant torques `tau`, a kernel
+// argument of this law alone).
+struct Impedance {
+    using Reg = const double*;
+    const double *kp, *kd, *qref;
+};
+
+// blf_fbd_euler_integrate_impedance_traj: the impedance with the reference indexed by the
+// integration step, slice s(i) = min(i / sps, T - 1) of qref [T][B][n], a velocity feed-forward
+// qdref (or null) and a per-system bias qbias (or null):
+//   r = qref (+ qbias),  tau = kp (r - q) - kd (qdot - qdref)   (qdref null: - kd qdot)
+// Two systems per wavefront: r and qdref of the current slice sit in LDS (r in Smem's q_ref slot,
+// qdref in n doubles behind Smem::total) and are restaged only at a step where the slice changes;
+// one system per wavefront reads them from global memory every step, as the held form reads qref.
+struct ImpedanceTraj {
+    using Reg = const double*;
+    const double *kp, *kd, *qref, *qdref, *qbias;
+    int64_t qdstride;
+    int32_t T, sps;
+};
+
+// blf_fbd_euler_integrate_computed_torque_traj: the trajectory law's schedule and slices with the
+// torque replaced by the inverse dynamics of the commanded acceleration,
 //   sdd = qddref + kp (qref + qbias - q) + kd (qdref - qdot),  tau = clamp(ID(sdd), tau_max),
 // taken at every step's start state (the torques pass through Smem's tq slot), followed by the
 // forward evaluation with that tau.  The references are read from global memory every step in both
-// layouts.
+// layouts.  Only the articulated-body path exists: the call refuses mass_reg, so the kernel's
+// regularisation argument is empty (a null pointer where one is read).
 struct ComputedTorqueTraj {
+    struct Reg {
+        __device__ operator const double*() const { return nullptr; }
+    };
     const double *kp, *kd, *qref, *qdref, *qddref, *qbias, *taumax;
     double* taulast;
     int64_t qdstride, qddstride;
     int32_t T, sps;
 };
 
-// Text of its own beside fbd_euler_traj_kernel, for that kernel's reason.  Only the
-// articulated-body path exists (the call refuses mass_reg); ABA stays a parameter so that an
+// ForwardEuler<FloatingBaseDynamicalSystem>::integrate under one of the laws above: the state and
+// (two systems per wavefront) the per-system constants staged in LDS, nsteps steps of the law's
+// torque, fbd_eval and the pose / velocity update, and the write-back (NaN where an evaluation
+// failed).  One text for the three laws, the law's blocks behind `if constexpr`: Tau is
+// `const double* __restrict__` under Impedance and empty otherwise, so every instantiation keeps
+// the argument layout, and with it the register allocation, of a kernel written for that law alone
+// (where a law's value is computed decides the allocation too, see tq
+// below).  ComputedTorqueTraj has no ABA = false instantiation; ABA stays a parameter so that an
 // instantiation is named like its neighbours'.
-template <int NVMAX, int HW, bool PRI, bool ABA>
-__global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_ctq_kernel(Model m, blf_fb_state st,
-                                                          Contacts ct, int32_t nsteps, double dT, double dT_last,
-                                                          ComputedTorqueTraj law, int64_t batch)
+// __launch_bounds__: two systems per wavefront (HW = 32) keep more state live per wave: capping it
+// at 256 VGPRs for two waves per SIMD spills (9.40 ms per c5 period), one wave per SIMD does not
+// (8.29 ms, against 9.29 ms with one system per wavefront at two waves per SIMD; tools/ab_c5.sh).
+// kCS, the per-system constants of the Euler loop staged in LDS: the two-systems form only (LLVM's
+// allocator crashes on the HW = 64 form).
+template <int NVMAX, int HW, bool PRI, bool ABA, class Law, class... Tau>
+__global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_kernel(Model m, blf_fb_state st, Tau... tau,
+                                                          Contacts ct, typename Law::Reg reg,
+                                                          int32_t nsteps, double dT, double dT_last,
+                                                          Law law, int64_t batch)
 {
-    static_assert(ABA, "computed torque: the articulated-body path only");
+    constexpr bool kHeld = std::is_same_v<Law, Impedance>, kTraj = std::is_same_v<Law, ImpedanceTraj>;
+    constexpr bool kCtq = std::is_same_v<Law, ComputedTorqueTraj>;
+    static_assert(kHeld || kTraj || kCtq, "an Euler torque law");
+    static_assert(ABA || !kCtq, "computed torque: the articulated-body path only");
+    static_assert(sizeof...(Tau) == (kHeld ? 1 : 0), "the constant torques: the held law's argument");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const Half<HW> H;
     const int n = m.n, NV = n + 6;
     constexpr bool kCS = HW == 32;
-    const Smem S(smem + H.half * Smem(nullptr, n, ct.C, ABA).total, n, ct.C, ABA);
+    const int nx = kTraj && kCS ? (n + 1) & ~1 : 0;   // the slice's qdref behind the system's Smem block
+    const Smem S(smem + H.half * (Smem(nullptr, n, ct.C, ABA).total + nx), n, ct.C, ABA);
     const int lane = H.hl;
-    constexpr int per = kWave / HW;
+    constexpr int per = kWave / HW;   // systems per wavefront
     const Topo T = build_topo<HW>(m, S);
     double* loc = S.st();   // bv 6 | jv n | bp 3 | bR 9 | jp n | dR 9
     double* dR = loc + 18 + 2 * n;
     const int64_t i0 = (int64_t)blockIdx.x * per + H.half;
-    const bool active = i0 < batch;   // see fbd_euler_kernel
+    // a system past the end of an odd batch is computed (as the last system's copy, beside its
+    // partner) and written nowhere
+    const bool active = i0 < batch;   // see fbd_dynamics_kernel
     const int64_t q = active ? i0 : batch - 1;
     for (int i = lane; i < 18 + 2 * n; i += HW) {
         double v;
@@ -1488,7 +1296,7 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_ctq_kernel(Mod
         else v = st.joint_pos[(int64_t)n * q + (i - 18 - n)];
         loc[i] = v;
     }
-    if constexpr (kCS) {
+    if constexpr (kCS) {   // this system's constants of the Euler loop, once (Smem o_cst / o_imp)
         const int C = ct.C;
         for (int i = lane; i < 29 * C; i += HW) {
             double v;
@@ -1502,42 +1310,113 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_ctq_kernel(Mod
             else v = ct.params[i - 25 * C];
             S.cst()[i] = v;
         }
+        if constexpr (kHeld) {
+            if (law.kp)
+                for (int j = lane; j < n; j += HW) {
+                    S.imp()[j] = law.kp[j];
+                    S.imp()[n + j] = law.kd[j];
+                    S.imp()[2 * n + j] = law.qref[(int64_t)n * q + j];
+                }
+        } else if constexpr (kTraj) {
+            for (int j = lane; j < n; j += HW) {
+                S.imp()[j] = law.kp[j];
+                S.imp()[n + j] = law.kd[j];
+            }
+        }
     }
     wave_sync();
     bool ok = true;
-    const double zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // where fbd_eval reads the step's torques: Smem's tq slot once a law has filled it (assigned in
+    // each law's branch: initialised here it moves the trajectory laws' register allocation), the
+    // held law without an impedance the constant ones
+    const double* tq = nullptr;
+    if constexpr (kHeld) tq = (tau, ...) + (int64_t)n * q;
+    int32_t slice = -1, left = 0;   // the trajectory law: the slice in use and the steps it still holds
     for (int32_t step = 0; step < nsteps; ++step) {
         const double h = step + 1 < nsteps ? dT : dT_last;
-        int64_t slice = step / law.sps;
-        if (slice > law.T - 1) slice = law.T - 1;   // the last slice is held to the end
-        const int64_t at = slice * batch + q;       // element (slice, q, .)
-        // the commanded joint accelerations of this step from its start state
-        for (int j = lane; j < n; j += HW) {
-            double r = law.qref[at * n + j];
-            if (law.qbias) r = r + law.qbias[(int64_t)n * q + j];
-            double a = law.kp[j] * (r - loc[18 + n + j]);
-            if (law.qdref) a = a + law.kd[j] * (law.qdref[at * law.qdstride + j] - loc[6 + j]);
-            else a = a - law.kd[j] * loc[6 + j];
-            if (law.qddref) a = law.qddref[at * law.qddstride + j] + a;
-            S.tq()[j] = a;
-        }
-        wave_sync();
-        double bo[6];
-        ok = fbd_id_eval<HW, PRI, kCS>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n, S.tq(), false,
-                                       zero6, bo, ct, q, T, loc + kRef(n)) && ok;
-        if (law.taumax) {   // (selects: a NaN torque stays NaN)
+        // the control input of this step from its start state, then the accelerations under it
+        if constexpr (kHeld) {
+            if (law.kp) {
+                for (int j = lane; j < n; j += HW) {
+                    if constexpr (kCS)
+                        S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * loc[6 + j];
+                    else
+                        S.tq()[j] = law.kp[j] * (law.qref[(int64_t)n * q + j] - loc[18 + n + j]) - law.kd[j] * loc[6 + j];
+                }
+                wave_sync();
+                tq = S.tq();
+            }
+        } else if constexpr (kTraj) {
+            double* const qdr = S.base + S.total;
+            const bool next = left == 0 && slice + 1 < law.T;   // the last slice is held to the end
+            if (next) {
+                ++slice;
+                left = law.sps;
+            }
+            --left;
+            const int64_t at = (int64_t)slice * batch + q;   // element (slice, q, .)
+            if constexpr (kCS) {
+                if (next)
+                    for (int j = lane; j < n; j += HW) {
+                        double r = law.qref[at * n + j];
+                        if (law.qbias) r = r + law.qbias[(int64_t)n * q + j];
+                        S.imp()[2 * n + j] = r;
+                        if (law.qdref) qdr[j] = law.qdref[at * law.qdstride + j];
+                    }
+            }
             for (int j = lane; j < n; j += HW) {
-                const double t = S.tq()[j], mx = law.taumax[j];
-                S.tq()[j] = t > mx ? mx : t < -mx ? -mx : t;
+                if constexpr (kCS) {
+                    if (law.qdref)
+                        S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * (loc[6 + j] - qdr[j]);
+                    else
+                        S.tq()[j] = S.imp()[j] * (S.imp()[2 * n + j] - loc[18 + n + j]) - S.imp()[n + j] * loc[6 + j];
+                } else {
+                    double r = law.qref[at * n + j];
+                    if (law.qbias) r = r + law.qbias[(int64_t)n * q + j];
+                    if (law.qdref)
+                        S.tq()[j] = law.kp[j] * (r - loc[18 + n + j]) - law.kd[j] * (loc[6 + j] - law.qdref[at * law.qdstride + j]);
+                    else
+                        S.tq()[j] = law.kp[j] * (r - loc[18 + n + j]) - law.kd[j] * loc[6 + j];
+                }
             }
             wave_sync();
+            tq = S.tq();
+        } else {
+            const double zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            int64_t sl = step / law.sps;
+            if (sl > law.T - 1) sl = law.T - 1;     // the last slice is held to the end
+            const int64_t at = sl * batch + q;      // element (slice, q, .)
+            // the commanded joint accelerations
+            for (int j = lane; j < n; j += HW) {
+                double r = law.qref[at * n + j];
+                if (law.qbias) r = r + law.qbias[(int64_t)n * q + j];
+                double a = law.kp[j] * (r - loc[18 + n + j]);
+                if (law.qdref) a = a + law.kd[j] * (law.qdref[at * law.qdstride + j] - loc[6 + j]);
+                else a = a - law.kd[j] * loc[6 + j];
+                if (law.qddref) a = law.qddref[at * law.qddstride + j] + a;
+                S.tq()[j] = a;
+            }
+            wave_sync();
+            double bo[6];
+            ok = fbd_id_eval<HW, PRI, kCS>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n, S.tq(), false,
+                                           zero6, bo, ct, q, T, loc + kRef(n)) && ok;
+            if (law.taumax) {   // (selects: a NaN torque stays NaN)
+                for (int j = lane; j < n; j += HW) {
+                    const double t = S.tq()[j], mx = law.taumax[j];
+                    S.tq()[j] = t > mx ? mx : t < -mx ? -mx : t;
+                }
+                wave_sync();
+            }
+            tq = S.tq();
         }
         ok = fbd_eval<NVMAX, HW, PRI, kCS, ABA>(m, S, loc, loc + 6, loc + 6 + n, loc + 9 + n, loc + 18 + n,
-                                                S.tq(), ct, q, nullptr, T, loc + kRef(n)) && ok;
+                                                tq, ct, q, reg, T, loc + kRef(n)) && ok;
         if (lane == 0) fbk_rot_rate(m.rho, loc + 9 + n, loc + 3, dR);
         wave_sync();
-        // positions first (they read the old velocities), then the velocities: fbd_euler_kernel
+        // every element moves by its derivative at the start of the step (ForwardEuler.tpp:37-45):
+        // positions first (they read the old velocities), then the velocities
         for (int i = lane; i < 12 + n; i += HW) {
+            // base position (3), base rotation (9), joint positions (n)
             if (i < 3) loc[6 + n + i] = loc[6 + n + i] + loc[i] * h;
             else if (i < 12) loc[6 + n + i] = loc[6 + n + i] + dR[i - 3] * h;
             else loc[18 + n + (i - 12)] = loc[18 + n + (i - 12)] + loc[6 + (i - 12)] * h;
@@ -1556,8 +1435,9 @@ __global__ __launch_bounds__(64, HW == 32 ? 1 : 2) void fbd_euler_ctq_kernel(Mod
             else if (i < 18 + n) st.base_rot[9 * q + (i - 9 - n)] = v;
             else st.joint_pos[(int64_t)n * q + (i - 18 - n)] = v;
         }
-        if (law.taulast && nsteps > 0)
-            for (int j = lane; j < n; j += HW) law.taulast[(int64_t)n * q + j] = ok ? S.tq()[j] : nan;
+        if constexpr (kCtq)
+            if (law.taulast && nsteps > 0)
+                for (int j = lane; j < n; j += HW) law.taulast[(int64_t)n * q + j] = ok ? S.tq()[j] : nan;
     }
 }
 
@@ -1606,35 +1486,62 @@ blf_status launch_fbd_dynamics(const blf_fb_model* md, const blf_fb_state* st, c
                      reg, *out, batch);
 }
 
+// fbd_euler_kernel's instantiation for one layout, `pri` and `aba` under a law.  A law without a
+// regularisation argument (ComputedTorqueTraj) has no mass-matrix form to pick.
+template <int NV, int HW, class Law, class... Tau>
+static auto fbd_euler_instance(bool pri, bool aba)
+{
+    if constexpr (std::is_same_v<typename Law::Reg, const double*>)
+        if (!aba) return pri ? fbd_euler_kernel<NV, HW, true, false, Law, Tau...> : fbd_euler_kernel<NV, HW, false, false, Law, Tau...>;
+    return pri ? fbd_euler_kernel<NV, HW, true, true, Law, Tau...> : fbd_euler_kernel<NV, HW, false, true, Law, Tau...>;
+}
+
+// The launch of fbd_euler_kernel under one law: `ext` bytes of LDS behind each system's block in
+// the two-systems layout, `tau` the law's leading kernel arguments (Tau as the kernel has it).
+template <class Law, class... Tau>
+static blf_status launch_euler_law(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
+                                   typename Law::Reg reg, int64_t batch, int32_t nsteps, double dT, double dT_last,
+                                   hipStream_t s, const Law& law, size_t ext, Tau... tau)
+{
+    const Contacts c = to_contacts(ct);
+    const bool pri = md->joint_type != nullptr;
+    bool aba = true;
+    if constexpr (std::is_same_v<typename Law::Reg, const double*>) aba = use_aba(reg);
+    const size_t lds = fbd_lds_bytes(md->ndof, c.C, aba);
+    return fb_launch("fbd_euler_kernel launch", fbd_euler_instance<32, 32, Law, Tau...>(pri, aba), lds + ext,
+                     fbd_euler_instance<kNW, kWave, Law, Tau...>(pri, aba), lds, md->ndof, batch, s, to_model(md), *st,
+                     tau..., c, reg, nsteps, dT, dT_last, law, batch);
+}
+
 blf_status launch_fbd_euler(const blf_fb_model* md, const blf_fb_state* st, const double* tau,
                             const blf_fb_contacts* ct, const double* reg, int64_t batch,
                             int32_t nsteps, double dT, double dT_last, hipStream_t s,
                             const blf_joint_impedance* impedance)
 {
-    const Contacts c = to_contacts(ct);
     Impedance imp{nullptr, nullptr, nullptr};
     if (impedance) imp = Impedance{impedance->kp, impedance->kd, impedance->q_ref};
-    const bool pri = md->joint_type != nullptr, aba = use_aba(reg);
-    const size_t lds = fbd_lds_bytes(md->ndof, c.C, aba);
-    return fb_launch("fbd_euler_kernel launch", FBD_KERNEL(fbd_euler_kernel, 32, 32), lds,
-                     FBD_KERNEL(fbd_euler_kernel, kNW, kWave), lds, md->ndof, batch, s, to_model(md), *st, tau, c, reg,
-                     nsteps, dT, dT_last, imp, batch);
+    return launch_euler_law<Impedance, const double* __restrict__>(md, st, ct, reg, batch, nsteps, dT, dT_last, s, imp,
+                                                                   0, tau);
 }
 
 blf_status launch_fbd_euler_traj(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
                                  const double* reg, int64_t batch, int32_t nsteps, double dT, double dT_last,
                                  hipStream_t s, const blf_joint_impedance_traj* it)
 {
-    const Contacts c = to_contacts(ct);
     const ImpedanceTraj imp{it->kp, it->kd, it->q_ref, it->qd_ref, it->q_bias, it->qd_stride, it->slices,
                             it->steps_per_slice};
-    const bool pri = md->joint_type != nullptr, aba = use_aba(reg);
-    const size_t lds = fbd_lds_bytes(md->ndof, c.C, aba);
     // two systems per wavefront: the slice's qdref behind each system's block (the kernel's nx)
     const size_t ext = sizeof(double) * (size_t)((md->ndof + 1) & ~1);
-    return fb_launch("fbd_euler_traj_kernel launch", FBD_KERNEL(fbd_euler_traj_kernel, 32, 32), lds + ext,
-                     FBD_KERNEL(fbd_euler_traj_kernel, kNW, kWave), lds, md->ndof, batch, s, to_model(md), *st, c, reg,
-                     nsteps, dT, dT_last, imp, batch);
+    return launch_euler_law(md, st, ct, reg, batch, nsteps, dT, dT_last, s, imp, ext);
+}
+
+blf_status launch_fbd_euler_ctq(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
+                                int64_t batch, int32_t nsteps, double dT, double dT_last, hipStream_t s,
+                                const blf_computed_torque_traj* it)
+{
+    const ComputedTorqueTraj law{it->kp, it->kd, it->q_ref, it->qd_ref, it->qdd_ref, it->q_bias, it->tau_max,
+                                 it->tau_last, it->qd_stride, it->qdd_stride, it->slices, it->steps_per_slice};
+    return launch_euler_law(md, st, ct, {}, batch, nsteps, dT, dT_last, s, law, 0);
 }
 
 blf_status launch_fb_invdyn(const blf_fb_model* md, const blf_fb_state* st, const double* joint_acc,
@@ -1647,21 +1554,6 @@ blf_status launch_fb_invdyn(const blf_fb_model* md, const blf_fb_state* st, cons
     return fb_launch("fb_invdyn_kernel launch", pri ? fb_invdyn_kernel<32, true> : fb_invdyn_kernel<32, false>, lds,
                      pri ? fb_invdyn_kernel<kWave, true> : fb_invdyn_kernel<kWave, false>, lds, md->ndof, batch, s,
                      to_model(md), *st, joint_acc, base_acc, c, tau, bout, status, batch);
-}
-
-blf_status launch_fbd_euler_ctq(const blf_fb_model* md, const blf_fb_state* st, const blf_fb_contacts* ct,
-                                int64_t batch, int32_t nsteps, double dT, double dT_last, hipStream_t s,
-                                const blf_computed_torque_traj* it)
-{
-    const Contacts c = to_contacts(ct);
-    const ComputedTorqueTraj law{it->kp, it->kd, it->q_ref, it->qd_ref, it->qdd_ref, it->q_bias, it->tau_max,
-                                 it->tau_last, it->qd_stride, it->qdd_stride, it->slices, it->steps_per_slice};
-    const bool pri = md->joint_type != nullptr;
-    const size_t lds = fbd_lds_bytes(md->ndof, c.C, true);
-    return fb_launch("fbd_euler_ctq_kernel launch",
-                     pri ? fbd_euler_ctq_kernel<32, 32, true, true> : fbd_euler_ctq_kernel<32, 32, false, true>, lds,
-                     pri ? fbd_euler_ctq_kernel<kNW, kWave, true, true> : fbd_euler_ctq_kernel<kNW, kWave, false, true>,
-                     lds, md->ndof, batch, s, to_model(md), *st, c, nsteps, dT, dT_last, law, batch);
 }
 
 blf_status launch_com_reference(const double* xi0, const double* vrp, int64_t vstride, const double* omega0,

@@ -1,5 +1,5 @@
-"""Timing of the inverse-dynamics kernels (csrc/fb_dynamics.hip: fb_invdyn_kernel, fbd_euler_ctq_kernel) on
-standing humanoids with both soles in contact (diagnostics; not the driver's bench.py).  HIP events around
+"""Timing of the inverse-dynamics kernels (csrc/fb_dynamics.hip: fb_invdyn_kernel and
+fbd_euler_kernel's ComputedTorqueTraj and ImpedanceTraj instantiations) on standing humanoids with both soles in contact (diagnostics; not the driver's bench.py).  HIP events around
 `reps` back-to-back calls after a warm-up, median of `rounds` rounds, the variants alternating within a
 round.  One JSON line each:
 
